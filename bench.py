@@ -16,11 +16,20 @@ librevrand_hip.so's C ABI (rr_comm_*, revrand_amd/parallel.py) -- there is no to
 
 Rank 0 prints ONE JSON line with the contract's keys plus
   roofline     -- algorithmic flops of one launch / HIP-event time of the kernel, vs the f32 MFMA peak of gfx950
-                  (157.3 TFLOP/s; MI355X_MICROARCH.md)
+                  (157.3 TFLOP/s; MI355X_MICROARCH.md), from the timed steps' own HIP events
+A plain run does only that: set up, warm up, time --steps steps, check trace(G) of the last one, print the line.
+With --full the line also carries
+  parity       -- the Gram of 2048 rows against the oracle, and (N=1) every entry of G and b against the f64 path
+  split_fp16_engine -- the same step on the opt-in fp16x3 Gram engine (N=1 only)
   cpu_baseline -- the NumPy restatement of revrand's path (oracle/, kind "port") timed on this box's host cores over a
                   bounded row sample (rank 0, N=1 only), SURVEY 8d's recipe: 200 000 rows, median of 3
   configs      -- BASELINE.json's other configurations on this GPU (N=1 only): C2, C3 (one GPU's share), C4, C5 and the
-                  headline shape in f64 arithmetic, each with its own roofline fraction and a bounded cpu sample.
+                  headline shape in f64 arithmetic, each with its own roofline fraction and a bounded cpu sample
+                  (N>1: the row-sharded configurations and the single-process run; --configs picks among them).
+
+--dump-outputs DIR writes what the last timed step computed -- the statistics [G | b | yty] a caller of the path receives --
+as float64 .npy files (G itself, or a fixed sample of its rows when it is larger than DUMP_G_BYTES); the inputs depend
+only on the arguments, so two builds compare output for output.
 """
 import argparse
 import faulthandler
@@ -69,6 +78,26 @@ def gen_chunk(c, rows, d, wvec):
     X = rng.standard_normal((rows, d), dtype=np.float32)
     y = np.sin(X @ wvec) + 0.1 * rng.standard_normal(rows, dtype=np.float32)
     return X, y.astype(np.float32)
+
+
+DUMP_G_BYTES = 32 << 20   # --dump-outputs: G in full up to this size (F <= 2048), else DUMP_G_ROWS of its rows
+DUMP_G_ROWS = 512         # (F = 4096: 16 MB, every 256 x 256 tile of the SYRK sampled; G is mirrored from its upper triangle)
+
+
+def dump_outputs(path, G, b, yty):
+    """--dump-outputs: the last timed step's statistics as float64 .npy files under `path`.  G larger than DUMP_G_BYTES is
+    written as DUMP_G_ROWS rows drawn with a fixed seed (G_rows, their indices in G_row_index) plus its whole diagonal."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"b": b, "yty": np.atleast_1d(yty)}
+    F = G.shape[0]
+    if G.nbytes <= DUMP_G_BYTES:
+        arrays["G"] = G
+    else:
+        rows = np.sort(np.random.default_rng(20261016).choice(F, min(DUMP_G_ROWS, F), replace=False))
+        arrays.update(G_rows=G[rows], G_row_index=rows.astype(np.float64), G_diag=np.diagonal(G).copy())
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 def runtime_info(_hip, parallel):
@@ -1759,7 +1788,7 @@ def single_process(args, json_out):
     # kernels loading the peers' HBM over the xGMI mesh) -- a second group of contexts on the same GPUs, after the timed
     # steps, on a thread that is given 90 s: a transport that has never run between two GPUs must not take the line with it
     pre_peer, peer_hung = None, False
-    if (group.transport == "rccl" or os.environ.get("RR_BENCH_FORCE_PEER_PREFLIGHT") == "1") \
+    if args.full and (group.transport == "rccl" or os.environ.get("RR_BENCH_FORCE_PEER_PREFLIGHT") == "1") \
             and os.environ.get("RR_BENCH_NO_PEER_PREFLIGHT") != "1":
         import threading
         box = {}
@@ -1788,6 +1817,10 @@ def single_process(args, json_out):
     trace_err = abs(float(np.trace(G)) - args.rows) / args.rows
     members_identical = all(np.array_equal(G, Gi) for Gi in Gs[1:])
     assert np.array_equal(G, G.T)
+    if args.dump_outputs:
+        sh0 = shards[0]
+        dump_outputs(args.dump_outputs, G, sh0.dev.download(sh0.acc, (F,), np.float64, offset_bytes=F * F * 8),
+                     sh0.dev.download(sh0.acc, (1,), np.float64, offset_bytes=(F * F + F) * 8))
     del Gs, G
     per_member = [float(np.mean([k[i][0] + k[i][1] + k[i][2] for k in kernel_ms])) for i in range(world)]
     syrk0 = float(np.mean([k[0][1] for k in kernel_ms]))
@@ -2002,7 +2035,7 @@ def single_process_under_ranks(args, comm, rank, world):
             env.pop("OMP_NUM_THREADS")
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--single-process", "--steps", str(min(args.steps, 5)),
                "--warmup", str(min(args.warmup, 2)), "--rows", str(args.rows), "--dist-rows", str(args.dist_rows),
-               "--config-timeout", str(args.config_timeout)]
+               "--config-timeout", str(args.config_timeout), "--full"]
         if args.no_parity_check:
             cmd.append("--no-parity-check")
         try:
@@ -2063,9 +2096,14 @@ def main():
                     help="seconds after which the self-launcher (--gpus N without a launcher) ends all ranks and fails")
     ap.add_argument("--config-timeout", type=float, default=900.0,
                     help="seconds one side configuration may take before every thread's stack is dumped and bench.py exits")
-    ap.add_argument("--configs", default="all",
-                    help="BASELINE's other configurations to time after the headline: all | none | e.g. c3,c5,headline (N=1); "
-                         "c3,elbo (N>1: the row-sharded _elbo evaluations)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the parity checks, the fp16x3 engine, the cpu baseline and BASELINE's "
+                         "other configurations (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's statistics (G or a fixed sample of its rows, b, yty) to DIR/<name>.npy")
+    ap.add_argument("--configs", default=None,
+                    help="with --full: BASELINE's other configurations to time after the headline (default all): all | none | "
+                         "e.g. c3,c5,headline (N=1); c3,elbo (N>1: the row-sharded _elbo evaluations)")
     ap.add_argument("--dist-rows", type=int, default=10_000_000,
                     help="global N of the N>1 configurations (BASELINE config 3: 10M; rehearsals on one GPU pass fewer)")
     ap.add_argument("--dist-rows-c4", type=int, default=None,
@@ -2078,6 +2116,12 @@ def main():
                     help="N GPUs behind ONE process: the in-process device group of StandardLinearModel(devices=N) "
                          "(revrand_amd/multigpu.py) instead of one rank per GPU; same line shape")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.configs is None:
+        args.configs = "all" if args.full else "none"
+    elif args.configs != "none" and not args.full:
+        ap.error("--configs %s: the side configurations run with --full" % args.configs)
     if args.dist_rows_c4 is None:
         args.dist_rows_c4 = 4_194_304 if args.dist_rows >= 10_000_000 else max(4096, int(args.dist_rows * 0.4194304))
     faulthandler.enable()  # a crash inside a library call leaves the Python stack on stderr
@@ -2218,7 +2262,7 @@ def main():
     # ---- parity of the measured path on a slice, off-diagonal entries included: Gram of the first rows against the
     # oracle (checker only) before anything is timed ----
     parity_err = None
-    if rank == 0 and my_rows >= 2048 and not args.no_parity_check:
+    if args.full and rank == 0 and my_rows >= 2048 and not args.no_parity_check:
         orc = _oracle()
         Xs, ys = gen_chunk(row0 // CH, min(CH, args.rows - (row0 // CH) * CH), d, wvec)
         lo = row0 - (row0 // CH) * CH
@@ -2261,12 +2305,15 @@ def main():
     diag = float(np.trace(G))
     assert np.array_equal(G, G.T) or os.environ.get("RR_GRAM_ABLATE")
     trace_err = abs(diag - args.rows) / args.rows
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, G, dev.download(acc_buf, (F,), np.float64, offset_bytes=F * F * 8),
+                     dev.download(acc_buf, (1,), np.float64, offset_bytes=(F * F + F) * 8))
 
     # ---- full-size parity (N = 1): EVERY entry of the timed step's G and b, over all rows, against the same statistics in
     # float64 arithmetic (rr_syrk_f64_kernel over float64 features of float64 X -- the route tests/test_gpu_rff.py holds to the
     # oracle at 1e-5): what the 2048-row oracle slice and the trace cannot see at N = 10M.  Untimed. ----
     full_check = None
-    if world == 1 and not use_comm and engine == "f32" and not args.no_parity_check and not os.environ.get("RR_GRAM_ABLATE") \
+    if args.full and world == 1 and not use_comm and engine == "f32" and not args.no_parity_check and not os.environ.get("RR_GRAM_ABLATE") \
             and my_rows <= 20_000_000 and os.environ.get("RR_BENCH_NO_FULL_CHECK") != "1":
         t_fc = time.perf_counter()
         b64 = _hip.RffHandle(W, compute="f64", device=local_rank)
@@ -2299,7 +2346,7 @@ def main():
 
     # ---- informational: the same step on the split-fp16 engine (N=1 only; never `value`) ----
     alt = None
-    if world == 1 and not use_comm and engine == "f32" and not args.no_alt_engine and not os.environ.get("RR_GRAM_ABLATE"):
+    if args.full and world == 1 and not use_comm and engine == "f32" and not args.no_alt_engine and not os.environ.get("RR_GRAM_ABLATE"):
         dev.set_gram_engine("fp16x3")
         step(False)
         dev.sync()
@@ -2424,7 +2471,7 @@ def main():
                 "fp16" if engine == "fp16x3" else "bf16", nprod)
         if alt:
             out["split_fp16_engine"] = alt
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(d, n, W, wvec, args.cpu_sample)
     ok = trace_err < (1e-6 if engine == "f32" else 1e-5) or os.environ.get("RR_GRAM_ABLATE")
 

@@ -245,7 +245,7 @@ def test_bench_two_ranks_as_the_driver_calls_it():
     """`python bench.py --gpus 2` (no launcher): starts its own ranks, exits 0, ONE JSON line, n_gpus as RCCL reports."""
     # (the single-process run inside the N > 1 line is rehearsed at 4 and 8 ranks below and by test_gpu_multigpu.py)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--rows", "600000", "--dist-rows", "20000", "--configs", "elbo"], capture_output=True, text=True, timeout=1500,
+                        "--rows", "600000", "--dist-rows", "20000", "--full", "--configs", "elbo"], capture_output=True, text=True, timeout=1500,
                        env=dict(os.environ, RR_BENCH_NO_SINGLE_PROCESS="1"))
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -281,7 +281,7 @@ def test_bench_two_ranks_under_torch_distributed_run_as_the_driver_launches_n_gp
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29577", os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--steps", "1", "--warmup", "1", "--rows", "600000", "--dist-rows", "20000",
-                        "--configs", "elbo"], capture_output=True, text=True, timeout=1500,
+                        "--full", "--configs", "elbo"], capture_output=True, text=True, timeout=1500,
                        env=dict(os.environ, RR_BENCH_NO_SINGLE_PROCESS="1"))
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -320,7 +320,7 @@ def test_bench_rehearsal_of_the_drivers_multi_gpu_call(world):
     # on this box's one GPU -- which the 8-way run covers)
     env = None if world == 8 else dict(os.environ, RR_BENCH_NO_SINGLE_PROCESS="1")
     extra = [] if world == 8 else ["--configs", "c3,elbo"]
-    r = _bench(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--rows", str(rows), "--dist-rows", str(drows)] + extra, env=env)
+    r = _bench(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--rows", str(rows), "--dist-rows", str(drows), "--full"] + extra, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -400,12 +400,40 @@ def test_bench_one_gpu_line_has_the_same_keys_under_a_launcher_environment():
     assert a["metric"] == b["metric"] and a["config"]["workload"] == b["config"]["workload"]
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_what_its_last_step_computed(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the headline only (no side configuration, cpu baseline,
+    second engine or oracle check), K timed steps; --dump-outputs holds the last step's [G | b | yty], checked here against
+    the oracle on the same seeded rows."""
+    import importlib.util
+    import revrand_oracle as orc
+    rows = 8192
+    r = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--rows", str(rows), "--dump-outputs", str(tmp_path)], timeout=600)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 / rows - 1) < 1e-3 and out["dtype"] == "f32"
+    assert not {"configs", "cpu_baseline", "split_fp16_engine"} & set(out)
+    assert out["config"]["parity_rel_err_2048_rows_vs_oracle"] is None and out["config"]["parity_all_rows_f32_vs_f64"] is None
+    got = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert sorted(got) == ["G_diag", "G_row_index", "G_rows", "b", "yty"] and all(a.dtype == np.float64 for a in got.values())
+    spec = importlib.util.spec_from_file_location("rr_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    X, y = bench.gen_chunk(0, rows, 32, np.random.RandomState(1).randn(32).astype(np.float32))
+    Gr, br, ytyr = orc.rff_gram_chunked(X.astype(np.float64), y.astype(np.float64), np.random.RandomState(42).randn(32, 2048), 1.0)
+    idx = got["G_row_index"].astype(np.int64)
+    assert normwise(got["G_rows"], Gr[idx]) < 1e-4 and normwise(got["G_diag"], np.diagonal(Gr)) < 1e-4
+    assert normwise(got["b"], br) < 1e-4 and abs(got["yty"][0] - ytyr) < 1e-6 * ytyr
+
+
 def test_bench_side_configuration_that_hangs_does_not_take_the_headline_line():
     """A side configuration stuck in a call that never returns: the watchdog dumps the stacks, writes the ONE JSON line with
     the headline and the configurations finished so far, marks the hung one, and the process exits 0."""
     env = dict(os.environ, RR_BENCH_TEST_HANG="posterior_F8257")
     r = _bench(["--rows", "300000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-alt-engine", "--no-parity-check",
-                "--configs", "posterior_f4096,posterior_f8257,predict_moments_n300k", "--config-timeout", "20"], env=env, timeout=900)
+                "--full", "--configs", "posterior_f4096,posterior_f8257,predict_moments_n300k", "--config-timeout", "20"], env=env, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines

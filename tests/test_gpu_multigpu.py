@@ -269,7 +269,7 @@ def test_bench_single_process_line():
     from conftest import ROOT
     env = dict(os.environ, RR_BENCH_FORCE_PEER_PREFLIGHT="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-process", "--steps", "2",
-                        "--warmup", "1", "--rows", "600000", "--dist-rows", "40000"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "1", "--rows", "600000", "--dist-rows", "40000", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and len(lines[0]) < 8192, lines

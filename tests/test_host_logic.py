@@ -578,6 +578,42 @@ def test_bench_line_is_numbers_only_and_small():
         bench.parity("x", float("nan"), 1e-4)
 
 
+def test_bench_side_configurations_need_full_and_steps_are_counted():
+    """A plain bench.py run times the headline only: asking for side configurations without --full, or for no timed step,
+    is refused before anything starts."""
+    import subprocess
+    import sys
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    for argv, says in ((["--configs", "c3"], "--full"), (["--steps", "0"], "--steps")):
+        r = subprocess.run([sys.executable, path] + argv, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and says in r.stderr and r.stdout == "", (argv, r.stderr[-1000:])
+
+
+def test_bench_dump_outputs_are_float64_fixed_and_bounded(tmp_path):
+    """--dump-outputs: [G | b | yty] as float64 .npy files; G in full when small, else the same seeded rows of it (and its
+    diagonal) on every run -- at F = 4096 well inside 64 MB."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("rr_bench", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    F = 4096
+    G = np.add.outer(np.arange(F, dtype=np.float64), np.arange(F, dtype=np.float64) * 1e-4)
+    b, yty = np.linspace(-1.0, 1.0, F), np.array([7.5])
+    names = bench.dump_outputs(str(tmp_path / "a"), G, b, yty)
+    assert names == ["G_diag", "G_row_index", "G_rows", "b", "yty"]
+    bench.dump_outputs(str(tmp_path / "b"), G, b, yty)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(os.path.getsize(str(tmp_path / "a" / (n + ".npy"))) for n in names) < 64e6
+    rows = got["G_row_index"].astype(np.int64)
+    assert len(np.unique(rows)) == bench.DUMP_G_ROWS and np.array_equal(got["G_rows"], G[rows])
+    assert np.array_equal(got["G_diag"], np.diagonal(G)) and np.array_equal(got["b"], b) and got["yty"].tolist() == [7.5]
+    assert np.array_equal(np.load(str(tmp_path / "b" / "G_row_index.npy")), got["G_row_index"])
+    small = G[:256, :256].astype(np.float32)
+    assert bench.dump_outputs(str(tmp_path / "c"), small, b[:256], 1.0) == ["G", "b", "yty"]
+    assert np.array_equal(np.load(str(tmp_path / "c" / "G.npy")), small.astype(np.float64))
+
+
 def test_sgd_stops_its_prefetch_worker_before_an_exception_of_the_objective_leaves_it():
     """when `fun` raises inside `sgd`, the traceback keeps the prefetching generator -- and its worker thread -- alive
     past the caller's cleanup (glm.fit frees the device buffers the worker's next batch writes to).  `sgd` closes the

@@ -36,7 +36,7 @@ if [ -n "$tests" ]; then
 fi
 for rep in $(seq 1 $reps); do
   for i in "${!ARMS[@]}"; do
-    env ${ARMS[$i]} timeout 1500 python bench.py --no-cpu-baseline --no-alt-engine $args --full-json $out/${i}_$rep.json > $out/${i}_$rep.line 2> $out/${i}_$rep.err
+    env ${ARMS[$i]} timeout 1500 python bench.py --full --no-cpu-baseline --no-alt-engine $args --full-json $out/${i}_$rep.json > $out/${i}_$rep.line 2> $out/${i}_$rep.err
   done
 done
 python - "$out" "${ARMS[@]}" <<'PY'

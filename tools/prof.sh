@@ -2,7 +2,7 @@
 # profiles/${ROUND}_* by tools/summarize.py.  Kernel traces and PMC passes are SEPARATE rocprofv3 runs (gpurun refuses
 # --pmc together with the hip / hsa / memory-copy trace domains).
 #   sh tools/prof.sh [stage ...]
-# stages (kernel trace + stats of `python bench.py --configs <that configuration>`):
+# stages (kernel trace + stats of `python bench.py --full --configs <that configuration>`):
 #   headline  elbo  elbo64  c3  ffelbo  posdef  predict  laplace  c4  c5  c1  c4gm  sp (bench.py --gpus 2 --single-process)
 # counter passes:
 #   sq     matrix-pipe busy cycles + clock of the headline kernels and of the two second-pass kernels (predictsq: predict_moments' product;
@@ -15,7 +15,7 @@ ROUND=${ROUND:-r06}
 OUT=gpurun_out/prof_$ROUND
 mkdir -p $OUT
 STAGES="${*:-headline elbo c3 ffelbo}"
-Q="--no-cpu-baseline --no-alt-engine --no-parity-check --config-timeout 600"
+Q="--full --no-cpu-baseline --no-alt-engine --no-parity-check --config-timeout 600"
 S="--rows 1000000 --steps 1 --warmup 0"
 kt() {  # kt <tag> <bench args...>: kernel trace + stats; the bench's unabridged record next to it
   tag=$1; shift
@@ -40,7 +40,7 @@ c5)       kt c5_kt $S --configs c5 ;;
 c1)       kt c1_kt $S --configs c1 ;;
 c4gm)     kt c4gm_kt $S --configs c4gm ;;
 c5small)  kt c5small_kt $S --configs c5small ;;
-sp)       timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/sp_kt -o kt -- python bench.py --gpus 2 --single-process --steps 3 --warmup 1 --rows 4000000 --dist-rows 1000000 --no-parity-check --full-json $OUT/sp_kt.full.json > $OUT/sp_kt.json 2> $OUT/sp_kt.err ;;
+sp)       timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/sp_kt -o kt -- python bench.py --gpus 2 --single-process --full --steps 3 --warmup 1 --rows 4000000 --dist-rows 1000000 --no-parity-check --full-json $OUT/sp_kt.full.json > $OUT/sp_kt.json 2> $OUT/sp_kt.err ;;
 sq)
   pmc headline_sq "$SQ" --rows 2000000 --steps 1 --warmup 0 --configs none
   pmc elbo_sq "$SQ" $S --configs c2_elbo_eval

@@ -161,7 +161,7 @@ for tag, name, key, dt in (("elbo_kt", "elbo", "C2_elbo_eval", "f32"), ("elbo64_
     npost = max(sum(v["calls"] for k, v in st.items() if k.startswith("rr_posterior_rows_kernel")), 1)
     post = {k.split("(")[0]: v["total_ms"] / npost for k, v in st.items()
             if k.replace("void ", "").startswith(("rr_gemm_tn_f64", "rr_chol_diag", "rr_syrk_f64", "rr_posterior_rows", "rr_assemble_ic", "rr_extract"))}
-    put(name, tag, {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --rows 1000000 --steps 1 --warmup 0 --configs %s (tools/prof.sh)" % key.lower(),
+    put(name, tag, {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --rows 1000000 --steps 1 --warmup 0 --configs %s (tools/prof.sh)" % key.lower(),
                     "config": cfg, "kernels": {k: v for k, v in ks.items() if v}, "posterior_kernels_ms_per_call": post, "all_kernels": st})
 
 # ---- config 3's one-GPU share: concatenated Gram + second pass ----
@@ -176,7 +176,7 @@ if b and "error" not in b.get("configs", {}).get(key, {"error": 1}):
           "rr_gemm_gradt_f32_kernel": by_totals(st, tr, "rr_gemm_gradt_f32_kernel", 2.0 * Ft * 2 * n3 + 2.0 * d3 * 2 * n3, N, ch, PEAK["f32"], "flop",
                                                 "second pass: the random Fourier child's 32 column tiles of U = Phi C (K = all 8257 features) contracted "
                                                 "in registers with both 32-column blocks of X; the linear child's columns are not computed")}
-    put("c3", "c3_kt", {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --rows 1000000 --steps 1 --warmup 0 --configs c3 (tools/prof.sh c3)",
+    put("c3", "c3_kt", {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --rows 1000000 --steps 1 --warmup 0 --configs c3 (tools/prof.sh c3)",
                         "config": cfg, "kernels": {k: v for k, v in ks.items() if v}, "all_kernels": st})
 
 # ---- FastFoodRBF _elbo at F = 16384 ----
@@ -197,7 +197,7 @@ if b and "error" not in b.get("configs", {}).get(key, {"error": 1}):
     npost = max(sum(v["calls"] for k, v in st.items() if k.startswith("rr_posterior_rows_kernel")), 1)
     post = {k.split("(")[0]: v["total_ms"] / npost for k, v in st.items()
             if k.replace("void ", "").startswith(("rr_gemm_tn_f64", "rr_chol_diag", "rr_syrk_f64", "rr_posterior_rows", "rr_assemble_ic", "rr_extract"))}
-    put("ff_elbo", "ffelbo_kt", {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --rows 1000000 --steps 1 --warmup 0 --configs c4elbo (tools/prof.sh ffelbo)",
+    put("ff_elbo", "ffelbo_kt", {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --rows 1000000 --steps 1 --warmup 0 --configs c4elbo (tools/prof.sh ffelbo)",
                                  "config": cfg, "kernels": {k: v for k, v in ks.items() if v}, "posterior_kernels_ms_per_call": post,
                                  "posterior_note": "kernel durations summed over the call's three concurrent streams (they exceed its wall-clock)",
                                  "all_kernels": st})
@@ -247,7 +247,7 @@ for tag, name, keys in (("posdef_kt", "posdef", ("posterior_F4096", "posterior_F
                                                   "Phi B with the upper-triangular factor B, column tiles paired into equal-cost workgroups, row sums of "
                                                   "squares in the epilogue: F^2 algorithmic flop per row (1.016 F^2 issued: in a diagonal block a wave skips the "
                                                   "k-blocks its column quarter of B is zero in; 1.0625 F^2 before that); the full-size calls", min_grid="max")
-    put(name, tag, {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --rows 1000000 --steps 1 --warmup 0 --configs %s (tools/prof.sh)" % ",".join(k.lower() for k in keys),
+    put(name, tag, {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --rows 1000000 --steps 1 --warmup 0 --configs %s (tools/prof.sh)" % ",".join(k.lower() for k in keys),
                     "configs": cfgs, "kernels": {k: v for k, v in ks.items() if v}, "all_kernels": st})
 
 
