@@ -73,6 +73,10 @@ int rr_build_flags(void);
  * device of the stream launched on" (the invariant of the in-process device group; a violation fails the next rr_ctx_sync
  * with the launch site named).  0 in a release build, which makes no such check. */
 int64_t rr_debug_launch_checks(void);
+/* RR_BUILD_BOUNDS builds: the number of launches of kernel `name` (its identifier, without template arguments) since the
+ * library was loaded or the counts were last reset; name == NULL resets every count and returns 0.  -1 in a release
+ * build, which does not count. */
+int64_t rr_debug_kernel_launches(const char *name);
 const char *rr_last_error(void);
 int rr_device_count(int *count);
 

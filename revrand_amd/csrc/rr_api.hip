@@ -61,8 +61,23 @@ static int guard_check_one(void *user, const GuardRec &r, const char *where) {
 
 static std::string g_launch_violation;  // first launch made with another device current than its stream's (under g_guard_mu)
 static long g_launch_checks = 0;
+static std::map<std::string, int64_t> g_kernel_launches;  // kernel identifier -> launches (under g_guard_mu)
 
-void rr_launch_device_check(hipStream_t s, const char *file, int line) {
+// "(rr_gemm_lik_f32_kernel<ID, ST>)" -> "rr_gemm_lik_f32_kernel": the launch macro's spelling without parentheses, blanks and
+// template arguments
+static std::string kernel_id(const char *spelled) {
+    std::string id;
+    for (const char *q = spelled; *q && *q != '<'; ++q)
+        if (*q != '(' && *q != ')' && *q != ' ') id += *q;
+    return id;
+}
+
+void rr_launch_device_check(hipStream_t s, const char *file, int line, const char *kernel) {
+    const std::string id = kernel_id(kernel);
+    {
+        std::lock_guard<std::mutex> lk(g_guard_mu);
+        ++g_kernel_launches[id];
+    }
     int cur = -1;
     hipDevice_t sd = -1;
     if (hipGetDevice(&cur) != hipSuccess || hipStreamGetDevice(s, &sd) != hipSuccess) {
@@ -129,6 +144,21 @@ int64_t rr_debug_launch_checks(void) {
     return (int64_t)rr_launch_checks_done();
 #else
     return 0;
+#endif
+}
+
+int64_t rr_debug_kernel_launches(const char *name) {
+#ifdef RR_BOUNDS
+    std::lock_guard<std::mutex> lk(g_guard_mu);
+    if (name == nullptr) {
+        g_kernel_launches.clear();
+        return 0;
+    }
+    auto it = g_kernel_launches.find(kernel_id(name));
+    return it == g_kernel_launches.end() ? 0 : it->second;
+#else
+    (void)name;
+    return -1;
 #endif
 }
 

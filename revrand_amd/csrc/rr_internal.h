@@ -157,12 +157,12 @@ int rr_guard_check(const char *where);  // RR_OK, or RR_ERR_HIP with the message
 // (3) every kernel launch checks that the calling thread's current device IS the device of the stream it launches on -- the
 //     invariant of the in-process device group (one context per member, hipSetDevice at the top of every entry point) that a
 //     one-GPU box cannot show broken.  A violation is remembered and fails the next rr_guard_check (rr_ctx_sync) with the
-//     launch site named.
-void rr_launch_device_check(hipStream_t s, const char *file, int line);
+//     launch site named.  The same call counts launches per kernel (rr_debug_kernel_launches: which route a product took).
+void rr_launch_device_check(hipStream_t s, const char *file, int line, const char *kernel);
 #undef hipLaunchKernelGGL
 #define hipLaunchKernelGGL(kernelName, numBlocks, numThreads, memPerBlock, streamId, ...)                              \
     do {                                                                                                               \
-        rr_launch_device_check((streamId), __FILE__, __LINE__);                                                        \
+        rr_launch_device_check((streamId), __FILE__, __LINE__, #kernelName);                                           \
         hipLaunchKernelGGLInternal((kernelName), (numBlocks), (numThreads), (memPerBlock), (streamId), __VA_ARGS__);   \
     } while (0)
 #define RR_DEV_ASSERT(cond)                                                                         \

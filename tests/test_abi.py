@@ -27,6 +27,18 @@ def test_library_exports_every_declared_symbol():
     assert lib.rr_abi_version() == 1
 
 
+def test_release_build_counts_no_launches():
+    """rr_debug_launch_checks / rr_debug_kernel_launches are the bounds-checking build's counters: the release library
+    makes no checks and counts nothing (-1: "not counted", not "never launched")."""
+    from revrand_amd import _hip
+    lib = _hip.load_library()
+    if lib.rr_build_flags() & 1:
+        pytest.skip("REVRAND_HIP_LIB is a bounds-checking build")
+    assert lib.rr_debug_launch_checks() == 0
+    assert lib.rr_debug_kernel_launches(b"rr_gemm_tn_f32_kernel") == -1
+    assert lib.rr_debug_kernel_launches(None) == -1
+
+
 def test_no_cpu_fallback_without_device():
     from revrand_amd import _hip
     from revrand_amd.basis_functions import RandomRBF

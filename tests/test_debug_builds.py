@@ -47,7 +47,11 @@ RAGGED = ["tests/test_gpu_rff.py::test_tiny_and_ragged_shapes_end_to_end", "test
           "tests/test_gpu_resident_group.py::test_group_resident_fit_equals_the_one_context_fit[two streams-gaussian-cat-devices2-host]",
           "tests/test_gpu_resident_group.py::test_group_resident_fit_equals_the_one_context_fit[one stream-binomial-iso-devices1-device]",
           "tests/test_gpu_resident_group.py::test_group_resident_fit_equals_the_one_context_fit[two streams-poisson-gm-devices4-host]",
-          "tests/test_gpu_resident_sgd.py::test_spectral_mixture_children_run_resident[two streams-12-gaussian]"]
+          "tests/test_gpu_resident_sgd.py::test_spectral_mixture_children_run_resident[two streams-12-gaussian]",
+          # every route of the GLM step's products and of `project`, bit for bit on integer data (ragged rows, F and S)
+          "tests/test_gpu_glm_routes.py::test_project_is_exact_on_every_route",
+          "tests/test_gpu_glm_routes.py::test_step_is_exact_on_every_route",
+          "tests/test_gpu_glm_routes.py::test_step_sequence_is_exact"]
 
 
 def _asan_runtime():
@@ -164,3 +168,29 @@ def test_bounds_build_checks_the_device_of_every_launch():
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, REVRAND_HIP_LIB=DEBUG_LIB), capture_output=True,
                        text=True, timeout=900)
     assert "checked" in r.stdout and "RR_BOUNDS" not in (r.stdout + r.stderr), (r.stdout[-1500:], r.stderr[-3000:])
+
+
+@pytest.mark.gpu
+def test_bounds_build_counts_the_kernel_each_route_takes():
+    """One GLM step (or projection) per case of tests/test_gpu_glm_routes.py under the bounds-checking build, which counts
+    launches per kernel (rr_debug_kernel_launches): each product ran on the kernel the module's route table names for this
+    device's CU count, and no other GEMM kernel ran -- the table stays honest if a rule of fm_gemm or glm_pipeline changes."""
+    if not os.path.exists(DEBUG_LIB):
+        pytest.skip("make -C revrand_amd/csrc debug has not been run")
+    code = (
+        "import json, sys; sys.path[:0] = [%r, %r, %r]\n"
+        "import test_gpu_glm_routes as R\n"
+        "print('CENSUS', json.dumps(R.census()))\n" % (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")))
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(os.environ, REVRAND_HIP_LIB=DEBUG_LIB),
+                       capture_output=True, text=True, timeout=900)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("CENSUS ")]
+    assert r.returncode == 0 and lines and "RR_BOUNDS" not in (r.stdout + r.stderr), (r.stdout[-1500:], r.stderr[-3000:])
+    import json
+    rows = json.loads(lines[-1][len("CENSUS "):])
+    bad = []
+    for label, cu, got, want in rows:
+        print("%-36s cu=%d %s" % (label, cu, " ".join("%s=%d" % (k.replace("_f32_kernel", "").replace("_kernel", ""), v)
+                                                      for k, v in sorted(got.items()) if v)))
+        if got != want:
+            bad.append((label, got, want))
+    assert len(rows) >= 30 and not bad, bad
