@@ -239,6 +239,52 @@ int rr_featmat_put_fastfood(rr_featmat *fm, rr_basis *fastfood, const void *dX, 
                             const double *lenscale, int n_ls, int64_t col0);
 int rr_featmat_put_host(rr_featmat *fm, const void *Phi, int dtype, int64_t ncols, int64_t ldphi, int64_t col0);
 int rr_featmat_gram(rr_featmat *fm, const void *dy, int y_dtype, double *dG, double *db, double *dyty);
+/* The rows of the current rr_featmat_begin as they sit in HBM, padding columns included: out host float32 (rows, ld) with
+ * ld = F rounded up to a multiple of 256.  For tests and diagnostics (what a put_* call wrote, and what it left alone). */
+int rr_featmat_download(rr_featmat *fm, float *out);
+
+/* ---- bases defined by centres: RadialBasis, SigmoidalBasis (basis_functions.py:616-815); PolynomialBasis (:496-576) ----
+ * With x_n a row of X, c_j row j of the centres C (M, d) and l the length scale -- one for every dimension (n_ls == 1) or
+ * one per dimension (n_ls == d):
+ *   RR_CENTRES_RADIAL   Phi = exp(-sum_i ((x_ni - c_ji) / (2 l_i^2))^2)            (:685-686: X and C are divided by 2 l^2
+ *                       BEFORE the squared distance -- the reference's arithmetic, not its docstring's |x - c|^2 / (2 l^2))
+ *                       dPhi_i = Phi ((x_ni - c_ji) / l_i^3)^2                         (:712-719)
+ *   RR_CENTRES_SIGMOID  Phi = 1 / (1 + exp(-sqrt(sum_i ((x_ni - c_ji) / l_i)^2)))     (:784)
+ *                       dPhi_i = -(|x_ni - c_ji| / l_i^2) Phi (1 - Phi)               (:809-815)
+ * The gradient has one entry per length scale: n_ls == 1 gives input dimension 0's term alone ((N, M)), like the random
+ * Fourier bases' isotropic gradient; n_ls == d gives (N, M, d), the reference's np.dstack layout.  Distances are formed
+ * from the differences (x - c), never from |x|^2 - 2 x.c + |c|^2.
+ * rr_centres_create: C host, row-major (M, d) float64 (`self.C`, :657-658); compute RR_F32 / RR_F64 = the arithmetic of
+ * rr_centres_transform / rr_centres_grad (host X (N, d) with leading dimension ldx in, host float64 Phi (N, M) / dPhi out,
+ * streamed in row chunks); any d.  The handle is an rr_basis: rr_basis_destroy frees it. */
+#define RR_CENTRES_RADIAL 0
+#define RR_CENTRES_SIGMOID 1
+int rr_centres_create(rr_ctx *ctx, int kind, int compute, int d, int M, const double *C, rr_basis **out);
+int rr_centres_transform(rr_basis *basis, const void *X, int x_dtype, int64_t N, int64_t ldx, const double *lenscale,
+                         int n_ls, double *Phi);
+int rr_centres_grad(rr_basis *basis, const void *X, int x_dtype, int64_t N, int64_t ldx, const double *lenscale, int n_ls,
+                    double *dPhi);
+/* Phi of the rows of the current rr_featmat_begin at columns [col0, col0 + M) of a feature matrix (f32 arithmetic, device X
+ * with ldx >= d, d <= 128; any col0 -- columns outside the block and the matrix' padding are left alone).  The P^T side
+ * copy is not written: consumers run their transposing pass.  The matrix remembers (basis, col0, length scales) for the
+ * contractions below. */
+int rr_featmat_put_centres(rr_featmat *fm, rr_basis *basis, const void *dX, int x_dtype, int64_t ldx,
+                           const double *lenscale, int n_ls, int64_t col0);
+/* PolynomialBasis.transform (:549-567) at columns [col0, col0 + include_bias + d order): [1], then x_i^1 .. x_i^order per
+ * input dimension i (dimension-major, power-minor). */
+int rr_featmat_put_poly(rr_featmat *fm, const void *dX, int x_dtype, int64_t ldx, int d, int order, int include_bias,
+                        int64_t col0);
+/* dg[i] += sum_{n,j} E_nj dPhi_i[n,j] for the n_ls entries of the length scales this basis' block at col0 was PUT with since
+ * rr_featmat_begin (the feature matrix records them per put: other calls on the same handle in between -- a stand-alone
+ * transform / grad, a put into another matrix -- do not change the result; a (basis, col0) that was not put is refused),
+ * without dPhi; dg: DEVICE float64 (n_ls).  rr_featmat_pass2_centres, after rr_featmat_pass2_rows: E = Err m^T - Phi C,
+ * so that slm.py:193-195's dhyp_i = -dg[i] / var.  rr_featmat_glm_centres, after a GLM step that stored EdPhi: E = EdPhi,
+ * glm.py:274-275's dhyp_i = -dg[i].  Float64 sums in two fixed-order stages (per-workgroup partials, then one thread per
+ * entry adds them in index order): no floating-point atomics, the same bits every run in every mode. */
+int rr_featmat_pass2_centres(rr_featmat *fm, rr_basis *basis, const void *dX, int x_dtype, int64_t ldx, int64_t col0,
+                             double *dg);
+int rr_featmat_glm_centres(rr_featmat *fm, rr_basis *basis, const void *dX, int x_dtype, int64_t ldx, int64_t col0,
+                           double *dg);
 
 /* ---- the same in FLOAT64: the feature matrix of a concatenation with a dtype="f64" child -------------------
  * BasisCat.transform's hstack (basis_functions.py:1599-1627) in float64 in HBM, reduced by the f64 MFMA SYRK

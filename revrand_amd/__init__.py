@@ -5,6 +5,7 @@ revrand's own Basis / StandardLinearModel interface.  See DESIGN.md.
 """
 from . import basis_functions, btypes, likelihoods  # noqa: F401
 from .btypes import Bound, Parameter, Positive  # noqa: F401
+from .basis_functions import PolynomialBasis, RadialBasis, SigmoidalBasis  # noqa: F401
 
 
 def __getattr__(name):

@@ -96,6 +96,21 @@ SIGNATURES = {
                                            ctypes.c_int64, ctypes.c_int64]),
     "rr_featmat_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "rr_featmat_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "rr_centres_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_void_p, _c_void_pp]),
+    "rr_centres_transform": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rr_centres_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rr_featmat_put_centres": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
+    "rr_featmat_put_poly": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "rr_featmat_pass2_centres": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "rr_featmat_glm_centres": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "rr_featmat64_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _c_void_pp]),
     "rr_featmat64_destroy": (None, [ctypes.c_void_p]),
     "rr_featmat64_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
@@ -898,7 +913,7 @@ class FeatureMatrix(object):
     def __init__(self, max_rows, F, device=None):
         self.dev = get_device(device)
         self.lib = self.dev.lib
-        self.F, self.max_rows = int(F), int(max_rows)
+        self.F, self.max_rows, self.rows = int(F), int(max_rows), 0
         h = ctypes.c_void_p()
         _check(self.lib, self.lib.rr_featmat_create(self.dev.ctx, self.max_rows, self.F, ctypes.byref(h)))
         self.h = h
@@ -913,6 +928,7 @@ class FeatureMatrix(object):
 
     def begin(self, rows):
         _check(self.lib, self.lib.rr_featmat_begin(self.h, rows))
+        self.rows = int(rows)
 
     def put_rff(self, handle, dX, lenscale, col0):
         ls, lsp, nls = _lenscale_arg(lenscale)
@@ -933,6 +949,30 @@ class FeatureMatrix(object):
         mu = np.ascontiguousarray(mean, dtype=np.float64)
         _check(self.lib, self.lib.rr_featmat_put_fastfood_gm(self.h, ff_handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld,
                                                              mu.ctypes.data_as(ctypes.c_void_p), lsp, nls, col0))
+
+    def download(self):
+        """The rows of the last `begin` as they sit in HBM, (rows, ld) float32 with the padding columns (rr_featmat_download)."""
+        out = np.empty((self.rows, (self.F + 255) // 256 * 256), dtype=np.float32)
+        _check(self.lib, self.lib.rr_featmat_download(self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def put_centres(self, handle, dX, lenscale, col0):
+        """RadialBasis / SigmoidalBasis features of the rows dX into columns [col0, col0 + M) (rr_featmat_put_centres)."""
+        ls, lsp, nls = _lenscale_arg(lenscale)
+        _check(self.lib, self.lib.rr_featmat_put_centres(self.h, handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, lsp, nls, col0))
+
+    def put_poly(self, dX, order, include_bias, col0):
+        """PolynomialBasis features of the rows dX into columns [col0, col0 + include_bias + d order)."""
+        _check(self.lib, self.lib.rr_featmat_put_poly(self.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, dX.shape[1], int(order),
+                                                      1 if include_bias else 0, col0))
+
+    def pass2_centres(self, handle, dX, col0, dg):
+        """dg += sum((Err m^T - Phi C) o dPhi_i) per length scale of a centres child, after pass2_rows."""
+        _check(self.lib, self.lib.rr_featmat_pass2_centres(self.h, handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, col0, _ptr(dg)))
+
+    def glm_centres(self, handle, dX, col0, dg):
+        """dg += sum(EdPhi o dPhi_i) per length scale of a centres child, after a GLM step."""
+        _check(self.lib, self.lib.rr_featmat_glm_centres(self.h, handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, col0, _ptr(dg)))
 
     def put_host(self, Phi, col0):
         Phi = as_float_matrix(Phi)
@@ -1451,6 +1491,51 @@ class FastFoodHandle(object):
         _check(self.lib, self.lib.rr_fastfood_gm_transform(self.h, X.ctypes.data_as(ctypes.c_void_p), rr_dtype(X.dtype), N, _ld(X),
                                                            mu.ctypes.data_as(ctypes.c_void_p), lsp, nls,
                                                            out.ctypes.data_as(ctypes.c_void_p), rr_dtype(out.dtype), 4 * self.n))
+        return out
+
+
+RR_CENTRES_RADIAL, RR_CENTRES_SIGMOID = 0, 1
+
+
+class CentresHandle(object):
+    """Device-resident RadialBasis / SigmoidalBasis (rr_centres_create): the centres live on the GPU."""
+
+    def __init__(self, C, kind, compute="f32", device=None):
+        self.dev = get_device(device)
+        self.lib = self.dev.lib
+        C = np.ascontiguousarray(C, dtype=np.float64)
+        self.M, self.d = C.shape
+        self.compute = {"f32": RR_F32, "f64": RR_F64}[compute]
+        h = ctypes.c_void_p()
+        _check(self.lib, self.lib.rr_centres_create(self.dev.ctx, {"radial": RR_CENTRES_RADIAL, "sigmoid": RR_CENTRES_SIGMOID}[kind],
+                                                    self.compute, self.d, self.M, C.ctypes.data_as(ctypes.c_void_p),
+                                                    ctypes.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            try:
+                self.lib.rr_basis_destroy(h)
+            except Exception:
+                pass
+
+    def transform(self, X, lenscale):
+        X = as_float_matrix(X)
+        N = X.shape[0]
+        out = np.empty((N, self.M))
+        ls, lsp, nls = _lenscale_arg(lenscale)
+        _check(self.lib, self.lib.rr_centres_transform(self.h, X.ctypes.data_as(ctypes.c_void_p), rr_dtype(X.dtype), N, _ld(X),
+                                                       lsp, nls, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def grad(self, X, lenscale):
+        X = as_float_matrix(X)
+        N = X.shape[0]
+        ls, lsp, nls = _lenscale_arg(lenscale)
+        out = np.empty((N, self.M) if nls == 1 else (N, self.M, self.d))
+        _check(self.lib, self.lib.rr_centres_grad(self.h, X.ctypes.data_as(ctypes.c_void_p), rr_dtype(X.dtype), N, _ld(X),
+                                                  lsp, nls, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
 

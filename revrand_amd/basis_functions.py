@@ -9,7 +9,9 @@ and these are interchangeable on this path.  What differs is where the arithmeti
   RandomCauchy, RandomMatern32/52, OrthogonalRBF) call ``rr_rff_transform`` / ``rr_rff_grad``;
 * those bases additionally expose ``gram(X, y, *params)`` -- the fused
   Phi -> (Phi^T Phi, Phi^T y, y^T y) accumulation (``rr_rff_gram``) that
-  ``StandardLinearModel`` uses so that Phi never has to exist.
+  ``StandardLinearModel`` uses so that Phi never has to exist;
+* ``transform`` / ``grad`` of RadialBasis and SigmoidalBasis call ``rr_centres_transform`` / ``rr_centres_grad``; they and
+  PolynomialBasis are children of the device feature matrix in concatenations and resident fits (``rr_centres.hip``).
 
 Host-side by design (as in the reference): sampling of W from a seeded
 ``RandomState`` (so seeds reproduce the reference's W bit-for-bit), parameter plumbing,
@@ -25,6 +27,7 @@ import inspect
 from functools import reduce, wraps
 from itertools import repeat
 
+import logging
 import threading
 
 import numpy as np
@@ -35,6 +38,8 @@ from sklearn.utils import check_random_state
 from . import _hip
 from .btypes import Bound, Parameter, Positive
 from .utils import atleast_list, atleast_tuple, issequence
+
+log = logging.getLogger(__name__)
 
 
 # --------------------------------------------------------------------------------------
@@ -575,6 +580,83 @@ class _ResidentFastFoodGM(_ResidentRFF):
         self.dTm.free()
 
 
+class _ResidentCentres(object):
+    """RadialBasis / SigmoidalBasis child: X resident as float32 (N, d); features by rr_featmat_put_centres, the length
+    scales' gradient contracted on the device against the second pass' (or the GLM step's) scratch into `dg` -- one float64
+    per length scale, summed in a fixed order (rr_featmat_pass2_centres / rr_featmat_glm_centres)."""
+
+    nparams = 1
+
+    def __init__(self, basis, X):
+        self.basis = basis
+        self.h = basis._handle()
+        self.dX = self.h.dev.upload_matrix(np.ascontiguousarray(X, dtype=np.float32))
+        self.dg = self.h.dev.zeros(basis.d * 8)
+
+    def put(self, fm, X, r0, rows, col0, params):
+        self.ls = self.basis._check_dim(self.basis.d, params[0] if params else None)
+        fm.put_centres(self.h, _hip.DeviceView(self.dX, r0, rows), self.ls, col0)
+
+    def gather(self, didx, M, dev=None, slot=None):
+        _gather_slot(self, didx, M, dev, slot)
+
+    def put_batch(self, fm, M, col0, params, slot=None):
+        self.ls = self.basis._check_dim(self.basis.d, params[0] if params else None)
+        fm.put_centres(self.h, _hip.DeviceView(_batch_buffer(self, slot), 0, M), self.ls, col0)
+
+    def batch(self, M):
+        """The rows the feature matrix was last filled from: the gathered minibatch, or the first M resident rows."""
+        cur = getattr(self, "_cur", None)
+        return _hip.DeviceView(cur if cur is not None else self.dX, 0, M)
+
+    def reset(self):
+        self.h.dev.memset(self.dg)
+
+    def grad(self, fm, r0, rows, col0):
+        fm.pass2_centres(self.h, _hip.DeviceView(self.dX, r0, rows), col0, self.dg)
+
+    def glm_grad(self, fm, M, col0):
+        """The same contraction against EdPhi of a GLM minibatch step (glm.py:274-275)."""
+        fm.glm_centres(self.h, self.batch(M), col0, self.dg)
+
+    def dhyp(self, var):
+        """``apply_grad(dhyps, basis.grad(X, lenscale))`` (slm.py:193-197; var = 1: glm.py:274-275): a scalar for one length
+        scale, else (d,)."""
+        n = int(np.size(self.ls))
+        g = self.h.dev.download(self.dg, (n,), np.float64)
+        with np.errstate(over="ignore", invalid="ignore"):
+            out = -g / var
+        return float(out[0]) if n == 1 else out
+
+    def release(self):
+        self.dX.free()
+        self.dg.free()
+        _free_batches(self)
+
+
+class _ResidentPoly(object):
+    """PolynomialBasis child: its X columns stay on the device, the powers are made there (rr_featmat_put_poly)."""
+
+    nparams = 0
+
+    def __init__(self, basis, X):
+        self.order, self.include_bias = basis.order, basis.include_bias
+        self.dX = _hip.get_device().upload_matrix(np.ascontiguousarray(X, dtype=np.float32))
+
+    def put(self, fm, X, r0, rows, col0, params):
+        fm.put_poly(_hip.DeviceView(self.dX, r0, rows), self.order, self.include_bias, col0)
+
+    def gather(self, didx, M, dev=None, slot=None):
+        _gather_slot(self, didx, M, dev, slot)
+
+    def put_batch(self, fm, M, col0, params, slot=None):
+        fm.put_poly(_hip.DeviceView(_batch_buffer(self, slot), 0, M), self.order, self.include_bias, col0)
+
+    def release(self):
+        self.dX.free()
+        _free_batches(self)
+
+
 def _gather_batch(dX, dXb, didx, M, dev=None):
     """Rows didx of the resident matrix dX into a (grow-only) batch matrix of the same layout; on `dev`'s stream (default:
     the context the data were uploaded through)."""
@@ -823,6 +905,10 @@ class MinibatchFeatures(object):
                 child.reset()
                 child.glm_grad(self.fm, self.M, col0)
                 g = child.dhyp(1.0)
+            elif isinstance(child, _ResidentCentres):
+                child.reset()
+                child.glm_grad(self.fm, self.M, col0)
+                g = [child.dhyp(1.0)]   # -(EdPhi o dPhi_i).sum(), contracted on the device
             elif isinstance(child, _ResidentRFF):
                 if not self.__dict__.pop("_planned", False):  # (planned: dT was zeroed before the step, which may have
                     child.reset()                              # accumulated it already -- glm_rff then returns at once)
@@ -1418,6 +1504,160 @@ class FastFoodGM(FastFoodRBF):
         return "{}(nbases={}, Xdim={}, mean={}, lenscale={}, regularizer={}, random_state={})".format(
             type(self).__name__, self.nbases, self.d, self.params[0], self.params[1], self.regularizer,
             self.random_state)
+
+
+# --------------------------------------------------------------------------------------
+# Polynomial and centre bases (reference: basis_functions.py:496-576, 616-815)
+# --------------------------------------------------------------------------------------
+
+def _in_device_group(basis=None):
+    """True on a member thread of a device group (`_hip.device_scope`): sharded multi-GPU fits do not cover the bases below,
+    which then decline their resident routes -- and say so (multigpu.ShardedFitState.make logs that one GPU is used; a
+    minibatch assembled on a member takes the generic child: the basis' `transform` output, uploaded)."""
+    inside = getattr(_hip._tls, "dev", None) is not None
+    if inside and basis is not None:
+        log.info("%s: no device-resident child inside a device group (devices=...); its transform output is uploaded instead",
+                 type(basis).__name__)
+    return inside
+
+
+class PolynomialBasis(Basis):
+    """[1, X^1, ..., X^order] (basis_functions.py:496-576): an optional bias column, then for every input dimension i its
+    powers x_i^1 .. x_i^order next to each other (column ``bias + i * order + p - 1``).  No hyper-parameters.  ``transform``
+    is host NumPy like LinearBasis'; inside a device feature matrix the powers are made on the GPU (rr_featmat_put_poly)."""
+
+    @slice_init
+    def __init__(self, order, include_bias=True, regularizer=None):
+        if order < 0:
+            raise ValueError("Polynomial order must be positive")
+        self.order = order
+        self.include_bias = include_bias
+        super(PolynomialBasis, self).__init__(regularizer)
+
+    @slice_transform
+    def transform(self, X):
+        N, D = X.shape
+        bias = int(bool(self.include_bias))
+        Phi = np.empty((N, bias + D * self.order))
+        if bias:
+            Phi[:, 0] = 1.
+        for p in range(1, self.order + 1):  # power p of dimension i sits at column bias + i * order + p - 1
+            Phi[:, bias + p - 1::self.order] = X ** p
+        return Phi
+
+    def _width(self, D):
+        return int(self.include_bias) + D * self.order
+
+    @slice_transform
+    def _put_features(self, X, fm, col0):
+        if self._width(X.shape[1]) == 0:
+            return
+        dX = fm.dev.upload_matrix(np.ascontiguousarray(X, dtype=np.float32))
+        fm.put_poly(dX, self.order, self.include_bias, col0)
+        fm.dev.sync()
+        dX.free()
+
+    @slice_transform
+    def _resident_child(self, X, dtype=None):
+        if dtype == "f64" or self._width(X.shape[1]) == 0 or _in_device_group(self):
+            return None
+        return _ResidentPoly(self, X)
+
+    def __repr__(self):
+        return "{}(order={}, include_bias={}, regularizer={})".format(type(self).__name__, self.order, self.include_bias,
+                                                                      self.regularizer)
+
+
+class RadialBasis(_LengthScaleBasis):
+    """Radial basis functions around given centres (basis_functions.py:616-728).  With s_i = 1 / (2 l_i^2):
+    ``Phi[n, j] = exp(-sum_i ((x_ni - c_ji) s_i)^2)`` -- the reference scales X and C by 1 / (2 l^2) BEFORE the squared
+    distance (:685-686), so the exponent is |x - c|^2 / (4 l^4), not its docstring's |x - c|^2 / (2 l^2); kept as computed.
+    ``grad``: ``Phi * ((x_ni - c_ji) / l_i^3)^2`` per entry of the length-scale vector -- (N, M) for an isotropic length
+    scale (input dimension 0's term only, as the reference's loop has it), (N, M, d) for ARD (:712-719).
+
+    ``transform`` / ``grad`` run on the GPU (rr_centres_transform / rr_centres_grad) in ``dtype`` arithmetic ("f32" default,
+    "f64"); returned arrays are float64.  There is no host fallback."""
+
+    _kind = "radial"
+
+    @slice_init
+    def __init__(self, centres, lenscale=Parameter(gamma(1.), Positive()), regularizer=None, dtype="f32"):
+        if dtype not in ("f32", "f64"):
+            raise ValueError("dtype must be 'f32' or 'f64'")
+        self.dtype = dtype
+        self.M, self.d = centres.shape
+        self.C = centres
+        self._init_lenscale(lenscale)
+        super(_LengthScaleBasis, self).__init__(regularizer)
+
+    # device handle: created on first use in this process (and per device context), never pickled
+    def _handle(self):
+        cache, key = _handle_cache(self)
+        h = cache.get(key)
+        if h is None:
+            h = cache[key] = _hip.CentresHandle(self.C, self._kind, compute=self.dtype)
+        return h
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_hip_handle", None)
+        return state
+
+    def get_dim(self, X):
+        return self.M
+
+    @slice_transform
+    def transform(self, X, lenscale=None):
+        """(N, M) float64."""
+        lenscale = self._check_dim(X.shape[1], lenscale)
+        return self._handle().transform(X, lenscale)
+
+    @slice_transform
+    def grad(self, X, lenscale=None):
+        """dPhi/dl: (N, M), or (N, M, d) for ARD length scales."""
+        lenscale = self._check_dim(X.shape[1], lenscale)
+        return self._handle().grad(X, lenscale)
+
+    @slice_transform
+    def _put_features(self, X, fm, col0, lenscale=None):
+        lenscale = self._check_dim(X.shape[1], lenscale)
+        if self.dtype != "f32" or self.d > 128:
+            return fm.put_host(self._handle().transform(X, lenscale), col0)
+        dX = fm.dev.upload_matrix(np.ascontiguousarray(X, dtype=np.float32))
+        fm.put_centres(self._handle(), dX, lenscale, col0)
+        fm.dev.sync()
+        dX.free()
+
+    def _make_child(self, X, dtype):
+        # the float64 feature matrix is not extended to these bases, nor are inputs wider than the centre tile's LDS budget
+        if dtype == "f64" or self.dtype != "f32" or X.shape[1] != self.d or self.d > 128 or _in_device_group(self):
+            return None
+        return _ResidentCentres(self, X)
+
+    @slice_transform
+    def _resident_child(self, X, dtype=None):
+        return self._make_child(X, dtype)
+
+    @slice_transform
+    def device_fit_state(self, X, y):
+        """(X, y) resident for a whole fit: a one-child CatFitState (features and the length scales' gradient on the device)."""
+        child = self._make_child(X, None)
+        if child is None:
+            return None
+        import types
+        return CatFitState(types.SimpleNamespace(get_dim=self.get_dim, bases=[self]), [child], X, y)
+
+    def __repr__(self):
+        return "{}(centres={}, lenscale={}, regularizer={})".format(type(self).__name__, self.C, self.params, self.regularizer)
+
+
+class SigmoidalBasis(RadialBasis):
+    """Logistic sigmoid of the scaled distance to given centres (basis_functions.py:731-815):
+    ``Phi[n, j] = 1 / (1 + exp(-sqrt(sum_i ((x_ni - c_ji) / l_i)^2)))``; ``grad``: ``-(|x_ni - c_ji| / l_i^2) Phi (1 - Phi)`` per
+    entry of the length-scale vector, with RadialBasis' shape rule.  ARD length scales work as they do in the reference
+    (through broadcasting there)."""
+
+    _kind = "sigmoid"
 
 
 # --------------------------------------------------------------------------------------

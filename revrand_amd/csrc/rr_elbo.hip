@@ -1511,6 +1511,15 @@ struct FmPass2 {
 
 float *rr_fm_pass2_pt(void *p) { return p ? ((FmPass2 *)p)->Pt : nullptr; }
 
+void rr_fm_pass2_views(void *p, float **U, float **err, float **m32, bool *have_rows, bool *have_edphi) {
+    const FmPass2 *s = (const FmPass2 *)p;
+    *U = s ? s->U : nullptr;
+    *err = s ? s->err : nullptr;
+    *m32 = s ? s->m32 : nullptr;
+    *have_rows = s != nullptr && s->have_rows;
+    *have_edphi = s != nullptr && s->have_edphi;
+}
+
 void rr_fm_pass2_free(void *p) {
     if (!p) return;
     FmPass2 *s = (FmPass2 *)p;

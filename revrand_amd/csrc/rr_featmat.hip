@@ -176,6 +176,7 @@ int rr_featmat_begin(rr_featmat *fm, int64_t rows) {
     fm->covered = 0;
     fm->pt_covered = 0;
     fm->spans.clear();
+    fm->centres_puts.clear();
     if (rows256 > rows)
         RR_CHECK_HIP(hipMemsetAsync(fm->P + rows * fm->ld, 0, (size_t)(rows256 - rows) * fm->ld * sizeof(float), fm->ctx->stream));
     const int64_t w = fm->ld - fm->F;
@@ -307,6 +308,15 @@ int rr_featmat_put_host(rr_featmat *fm, const void *Phi, int dtype, int64_t ncol
         return RR_ERR_HIP;
     }
     return rr_fm_claim(fm, col0, ncols, "rr_featmat_put_host");
+}
+
+int rr_featmat_download(rr_featmat *fm, float *out) {
+    RR_REQUIRE(fm != nullptr && (out != nullptr || fm->rows == 0), "rr_featmat_download: null argument");
+    if (fm->rows == 0) return RR_OK;
+    RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
+    RR_CHECK_HIP(hipMemcpyAsync(out, fm->P, (size_t)fm->rows * fm->ld * sizeof(float), hipMemcpyDeviceToHost, fm->ctx->stream));
+    RR_CHECK_HIP(hipStreamSynchronize(fm->ctx->stream));
+    return RR_OK;
 }
 
 // y^T y into *dyty: atomics, or (deterministic mode) per-block partials added in order

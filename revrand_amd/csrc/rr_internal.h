@@ -40,7 +40,7 @@ struct rr_ctx {
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
 };
 
-enum rr_kind { RR_KIND_RFF = 0, RR_KIND_FASTFOOD = 1 };
+enum rr_kind { RR_KIND_RFF = 0, RR_KIND_FASTFOOD = 1, RR_KIND_CENTRES = 2 };
 constexpr int RR_MAX_XDIM = 4096;  // random Fourier bases: largest input dimension
 
 struct rr_basis {
@@ -77,6 +77,8 @@ struct rr_basis {
     float *ffB32 = nullptr, *ffG32 = nullptr, *ffSrad32 = nullptr, *ffSrev32 = nullptr, *ffL32 = nullptr;
     double *ffB64 = nullptr, *ffG64 = nullptr, *ffSrad64 = nullptr, *ffSrev64 = nullptr, *ffL64 = nullptr;
     int *ffPI = nullptr;
+    // RadialBasis / SigmoidalBasis (kind == RR_KIND_CENTRES): CentresData of rr_centres.hip; d = input dimension, n = centres
+    void *centres = nullptr;
 };
 
 void rr_set_error(const char *fmt, ...);
@@ -204,6 +206,7 @@ int rr_pick_dmax(int d);
 void rr_pass2_scratch_free(void *p);
 void rr_pass2d_scratch_free(void *p);
 void rr_posdef_scratch_free(void *p);
+void rr_centres_data_free(void *p);  // rr_centres.hip
 
 // Device feature matrix of a concatenated basis (rr_featmat.hip; second pass in rr_elbo.hip).
 struct rr_featmat {
@@ -220,6 +223,14 @@ struct rr_featmat {
     // the column intervals [c0, c1) put since rr_featmat_begin, kept sorted: a put that overlaps an earlier one is refused
     // (rr_fm_claim), so `covered == F` means every column was written exactly once -- not merely that widths add up
     std::vector<std::pair<int64_t, int64_t>> spans;
+    // rr_featmat_put_centres since rr_featmat_begin: which centres basis sits at which column, written with which length scales
+    // -- what rr_featmat_pass2_centres / rr_featmat_glm_centres contract against (the handle's own cache may have moved on)
+    struct CentresPut {
+        const rr_basis *basis;
+        int64_t col0;
+        std::vector<double> ls;
+    };
+    std::vector<CentresPut> centres_puts;
 };
 int rr_fm_claim(rr_featmat *fm, int64_t col0, int64_t width, const char *who);  // rr_featmat.hip
 // rr_featmat_put_rff with the length scales in device memory (rr_featmat.hip; the resident SVI loop of rr_elbo.hip)
@@ -227,6 +238,9 @@ int rr_fm_put_rff_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, 
                       int64_t col0, const double *dshift = nullptr, double sgn = 0.0);
 void rr_fm_pass2_free(void *p);
 float *rr_fm_pass2_pt(void *p);  // FmPass2::Pt or null
+// what a child's gradient contraction outside rr_elbo.hip reads of the second pass' / GLM step's scratch (p may be null):
+// U = Phi C or EdPhi (ld of the matrix), err (rows), m32 (F); have_rows / have_edphi: which of the two U holds
+void rr_fm_pass2_views(void *p, float **U, float **err, float **m32, bool *have_rows, bool *have_edphi);
 rr_ctx *rr_comm_ctx(rr_comm *comm);  // the context a communicator was bound to (rr_comm.hip)
 // Consumers of the feature matrix call this first: every column of [0, F) must have been put since rr_featmat_begin.
 #define RR_FM_REQUIRE_FILLED(fm, who)                                                                              \
