@@ -16,6 +16,27 @@
 
 #include "rr_internal.h"
 
+// A chain-kernel launch.  The bounds-checking build counts it under an identifier that names the instance --
+// family/R<registers>/<vx|phi|gm>, and for the lane-major families /<vec|scalar>/<full|partial> -- because the launch
+// macro's own spelling of a kernel held in a variable is just that variable's name (rr_debug_kernel_launches; no '<', '('
+// or blank, so the identifier is kept whole).  The release build is the plain launch.
+#ifdef RR_BOUNDS
+#include <string>
+static std::string ff_instance_id(const char *family, int R, bool phi, bool gm, int vec, int full) {
+    std::string id = std::string(family) + "/R" + std::to_string(R) + (gm ? "/gm" : phi ? "/phi" : "/vx");
+    if (vec >= 0) id += std::string(vec ? "/vec" : "/scalar") + (full ? "/full" : "/partial");
+    return id;
+}
+#define RR_FF_LAUNCH(family, R, phi, gm, vec, full, kern, grid, stream, ...)                                   \
+    do {                                                                                                        \
+        rr_launch_device_check((stream), __FILE__, __LINE__, ff_instance_id(family, R, phi, gm, vec, full).c_str()); \
+        hipLaunchKernelGGLInternal((kern), (grid), dim3(256), 0, (stream), __VA_ARGS__);                        \
+    } while (0)
+#else
+#define RR_FF_LAUNCH(family, R, phi, gm, vec, full, kern, grid, stream, ...) \
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, __VA_ARGS__)
+#endif
+
 template <typename TC>
 __device__ __forceinline__ void ff_sincos_rev(TC t, TC &s, TC &c);
 template <>
@@ -747,9 +768,10 @@ static int ff_launch(rr_basis *b, const void *dX, int64_t N, int64_t ldx, void *
         static int occ = 0;                                                                                          \
         if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, 0) != hipSuccess || occ < 1)) occ = 2; \
         const int64_t rp = rows_per_wg(occ);                                                                         \
-        hipLaunchKernelGGL(kern, dim3(gx16, (unsigned)((N + rp - 1) / rp)), dim3(256), 0, c->stream, (const TX *)dX, N, ldx, \
-                           b->d, k, (const double *)Bm, (const double *)Gm, b->ffPI, (const double *)Sm,             \
-                           (const double *)Lm, (TO *)dOut, ldo, (double)scale, (int)rp, (const double *)Mm);         \
+        RR_FF_LAUNCH("rr_fastfood16d_kernel", RR, PHI, GM, VEC, FULL, kern, dim3(gx16, (unsigned)((N + rp - 1) / rp)),   \
+                     c->stream, (const TX *)dX, N, ldx, b->d, k, (const double *)Bm, (const double *)Gm, b->ffPI,    \
+                     (const double *)Sm, (const double *)Lm, (TO *)dOut, ldo, (double)scale, (int)rp,                \
+                     (const double *)Mm);                                                                            \
     } while (0)
 #define RR_FF16D(RR)                                \
     do {                                            \
@@ -796,9 +818,9 @@ static int ff_launch(rr_basis *b, const void *dX, int64_t N, int64_t ldx, void *
         static int occ = 0;                                                                                          \
         if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, 0) != hipSuccess || occ < 1)) occ = 4; \
         const int64_t rp = rows_per_wg(occ);                                                                         \
-        hipLaunchKernelGGL(kern, dim3(gx16, (unsigned)((N + rp - 1) / rp)), dim3(256), 0, c->stream, (const TX *)dX, N, ldx, \
-                           b->d, k, (const float *)Bm, (const float *)Gm, b->ffPI, (const float *)Sm, (const float *)Lm, \
-                           (TO *)dOut, ldo, (float)scale, (int)rp, (const float *)Mm);                               \
+        RR_FF_LAUNCH("rr_fastfood16_kernel", RR, PHI, GM, VEC, FULL, kern, dim3(gx16, (unsigned)((N + rp - 1) / rp)),    \
+                     c->stream, (const TX *)dX, N, ldx, b->d, k, (const float *)Bm, (const float *)Gm, b->ffPI,      \
+                     (const float *)Sm, (const float *)Lm, (TO *)dOut, ldo, (float)scale, (int)rp, (const float *)Mm); \
     } while (0)
 #define RR_FF16(RR)                                \
     do {                                           \
@@ -819,9 +841,9 @@ static int ff_launch(rr_basis *b, const void *dX, int64_t N, int64_t ldx, void *
             return RR_OK;
         }
     }
-#define RR_FF(RR)                                                                                              \
-    hipLaunchKernelGGL((rr_fastfood_kernel<RR, PHI, TX, TC, TO>), grid, dim3(256), 0, c->stream, (const TX *)dX, N, \
-                       ldx, b->d, d2, k, Bm, Gm, b->ffPI, Sm, Lm, (TO *)dOut, ldo, scale, (int)rpb)
+#define RR_FF(RR)                                                                                                  \
+    RR_FF_LAUNCH("rr_fastfood_kernel", RR, PHI, false, -1, -1, (rr_fastfood_kernel<RR, PHI, TX, TC, TO>), grid, c->stream, \
+                 (const TX *)dX, N, ldx, b->d, d2, k, Bm, Gm, b->ffPI, Sm, Lm, (TO *)dOut, ldo, scale, (int)rpb)
     switch (R) {
         case 1: RR_FF(1); break;
         case 2: RR_FF(2); break;

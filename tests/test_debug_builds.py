@@ -51,7 +51,10 @@ RAGGED = ["tests/test_gpu_rff.py::test_tiny_and_ragged_shapes_end_to_end", "test
           # every route of the GLM step's products and of `project`, bit for bit on integer data (ragged rows, F and S)
           "tests/test_gpu_glm_routes.py::test_project_is_exact_on_every_route",
           "tests/test_gpu_glm_routes.py::test_step_is_exact_on_every_route",
-          "tests/test_gpu_glm_routes.py::test_step_sequence_is_exact"]
+          "tests/test_gpu_glm_routes.py::test_step_sequence_is_exact",
+          # every instance of the FastFood chain kernels on integer data and at exactly known phases: scalar and vector
+          # accesses, part waves, one to nine rows, offset pointers and leading dimensions into sentinel-filled buffers
+          "tests/test_gpu_fastfood_exact.py"]
 
 
 def _asan_runtime():
@@ -194,3 +197,37 @@ def test_bounds_build_counts_the_kernel_each_route_takes():
         if got != want:
             bad.append((label, got, want))
     assert len(rows) >= 30 and not bad, bad
+
+
+@pytest.mark.gpu
+def test_bounds_build_counts_the_fastfood_instance_each_case_runs():
+    """Every chain-kernel call of tests/test_gpu_fastfood_exact.py (census_runs: the case lists and the rows-per-block, grid
+    clamp, chunk seam and feature-matrix cases) under the bounds-checking build, which counts each FastFood launch under
+    an identifier naming its instance (family / registers / mode / vec or scalar / full or partial): the case ran the instance
+    the module's table names and no other FastFood instance -- by default, and under RR_FASTFOOD_OLD=1 (the lane-minor kernel
+    at 16 <= d2 <= 256).  Together the cases run every reachable instance."""
+    if not os.path.exists(DEBUG_LIB):
+        pytest.skip("make -C revrand_amd/csrc debug has not been run")
+    import json
+    code = (
+        "import json, sys; sys.path[:0] = [%r, %r, %r]\n"
+        "import test_gpu_fastfood_exact as E\n"
+        "print('CENSUS', json.dumps(E.census()))\n" % (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")))
+    ran, bad = {}, []
+    for extra in ({}, {"RR_FASTFOOD_OLD": "1"}):
+        env = dict(os.environ, REVRAND_HIP_LIB=DEBUG_LIB, **extra)
+        if not extra:
+            env.pop("RR_FASTFOOD_OLD", None)
+        r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+        lines = [l for l in r.stdout.splitlines() if l.startswith("CENSUS ")]
+        assert r.returncode == 0 and lines and "RR_BOUNDS" not in (r.stdout + r.stderr), (r.stdout[-1500:], r.stderr[-3000:])
+        for label, got, want in json.loads(lines[-1][len("CENSUS "):]):
+            if set(got) != {want}:
+                bad.append((label, got, want))
+            ran.setdefault(want, label)
+    for name in sorted(ran):
+        print("%-52s %s" % (name, ran[name]))
+    import test_gpu_fastfood_exact as E
+    reachable = E.reachable_idents()
+    assert not bad, bad
+    assert set(ran) == reachable, (sorted(reachable - set(ran)), sorted(set(ran) - reachable))
