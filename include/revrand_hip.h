@@ -394,6 +394,29 @@ int rr_featmat_glm_edphi(rr_featmat *fm, int64_t col0, int64_t ncols, double *E)
 /* out (rows, S) = P W for a host (F, S) float64 matrix: the latent function samples of glm.py:572-620. */
 int rr_featmat_project(rr_featmat *fm, const double *W, int S, double *out);
 
+/* ---- predictive statistics of the generalised linear model on the device (glm.py:324-570) --------------------------
+ * What GeneralizedLinearModel.predict_moments / predict_logpdf / predict_cdf / predict_interval reduce the latent samples
+ * f = Phi w to, per query row, without the (rows, S) matrix leaving HBM.  All arithmetic after the GEMM is float64. */
+#define RR_PRED_MOMENTS 0  /* out (rows, 2): mean and variance over the samples of Ey(f)                  :351-393 */
+#define RR_PRED_LOGPDF 1   /* out (rows, 3): mean, min, max over the samples of loglike(y_r, f)           :395-444 */
+#define RR_PRED_CDF 2      /* out (rows, 3): mean, min, max over the samples of cdf(q, f)                 :446-495 */
+#define RR_PRED_INTERVAL 3 /* out (rows, 2): the p_lo and p_hi quantiles of the sample-averaged CDF       :497-570 */
+/* W: host (F, S) float64 as for rr_featmat_project, whose transposing pass and GEMM this call repeats (S == 1 included);
+ * the reduction kernel then runs on the product and only `out` (host float64, row-major) is downloaded.
+ * lik, lik_param: RR_LIK_*, the Gaussian's variance.  rowarg: host (rows,) float64, the binomial's n; NULL otherwise.
+ * yq: RR_PRED_LOGPDF: host (rows,) float64 targets; RR_PRED_CDF: ONE float64, the quantile; NULL otherwise.
+ * RR_PRED_INTERVAL: per row centre = mean Ey, bracket [-reach, reach] with reach = 1000 max(centre, 1), 100 halvings on
+ * `mean cdf(mid) < p`; 0.5 (lo + hi), or NaN where the bracket does not straddle p -- for p = p_lo and p = p_hi. */
+int rr_featmat_predictive(rr_featmat *fm, const double *W, int S, int what, int lik, double lik_param, const double *rowarg,
+                          const double *yq, double p_lo, double p_hi, double *out);
+/* The likelihoods' functions by themselves, elementwise on host float64 arrays of n elements, through the device functions
+ * of the predictive kernels: out[i] = loglike(y[i], f[i]) / Ey(f[i]) / cdf(y[i], f[i]); rowarg as above (n elements). */
+#define RR_EVAL_LOGLIKE 0
+#define RR_EVAL_EY 1
+#define RR_EVAL_CDF 2
+int rr_lik_eval(rr_ctx *ctx, int what, int lik, double lik_param, const double *y, const double *f, const double *rowarg,
+                int64_t n, double *out);
+
 /* ---- the SVI loop of GeneralizedLinearModel.fit with its parameters resident (round 5) ----------------------------
  * Replaces, for a model whose basis is a random Fourier basis, a linear basis or a concatenation of such children (Xdim <= 128
  * each) and whose minibatches are gathered on the device, the host loop  sgd (optimize/sgd.py:337-425)  o  logtrick_sgd

@@ -163,6 +163,11 @@ SIGNATURES = {
                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "rr_featmat_glm_edphi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "rr_featmat_project": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "rr_featmat_predictive": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_void_p]),
+    "rr_lik_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "rr_glm_sgd_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),
@@ -1105,9 +1110,69 @@ class FeatureMatrix(object):
                                                      out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def predictive(self, rows, W, what, lik, lik_param=0.0, rowarg=None, y=None, quantile=None, p_lo=0.0, p_hi=0.0):
+        """Per-row statistics of the latent samples P W under a likelihood, reduced on the device (rr_featmat_predictive):
+        what = "moments" -> (rows, 2) [Ey, Vy]; "logpdf" (y: (rows,) targets) / "cdf" (quantile: a scalar) -> (rows, 3) [mean,
+        min, max over the samples]; "interval" -> (rows, 2), the p_lo and p_hi quantiles of the sample-averaged CDF.  lik,
+        lik_param, rowarg as a likelihood's ``predictive_spec`` returns them (rowarg: (rows,), the binomial's n)."""
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[0] != self.F:
+            raise ValueError("W must have shape (F, S)")
+        if what not in PREDICTIVE_IDS:
+            raise ValueError("what must be one of %s" % (sorted(PREDICTIVE_IDS),))
+
+        def per_row(a, name):
+            a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+            if a.shape[0] != rows:
+                raise ValueError("%s must have one entry per row" % name)
+            return a
+        rowarg = None if rowarg is None else per_row(rowarg, "rowarg")
+        yq = None
+        if what == "logpdf":
+            if y is None:
+                raise ValueError("the log density needs its targets")
+            yq = per_row(y, "y")
+        elif what == "cdf":
+            if quantile is None:
+                raise ValueError("the CDF needs its quantile")
+            yq = np.array([float(quantile)])
+        out = np.empty((rows, 3 if what in ("logpdf", "cdf") else 2))
+        none = ctypes.c_void_p(None)
+        _check(self.lib, self.lib.rr_featmat_predictive(
+            self.h, W.ctypes.data_as(ctypes.c_void_p), W.shape[1], PREDICTIVE_IDS[what], int(lik), float(lik_param),
+            none if rowarg is None else rowarg.ctypes.data_as(ctypes.c_void_p),
+            none if yq is None else yq.ctypes.data_as(ctypes.c_void_p), float(p_lo), float(p_hi),
+            out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
     def gram_into(self, dy, dG, db=None, dyty=None):
         _check(self.lib, self.lib.rr_featmat_gram(self.h, _ptr(dy), rr_dtype(dy.dtype) if dy is not None else 0,
                                                   _ptr(dG), _ptr(db), _ptr(dyty)))
+
+
+PREDICTIVE_IDS = {"moments": 0, "logpdf": 1, "cdf": 2, "interval": 3}   # RR_PRED_*
+LIK_EVAL_IDS = {"loglike": 0, "Ey": 1, "cdf": 2}                        # RR_EVAL_*
+
+
+def lik_eval(what, lik, f, y=None, lik_param=0.0, rowarg=None, device=None):
+    """loglike(y, f) / Ey(f) / cdf(y, f) of likelihood id `lik`, elementwise in float64 on the GPU through the device functions
+    of the predictive kernels (rr_lik_eval); y, f, rowarg broadcast against each other."""
+    if what not in LIK_EVAL_IDS:
+        raise ValueError("what must be one of %s" % (sorted(LIK_EVAL_IDS),))
+    dev = get_device(device)
+    arrs = [np.asarray(f, dtype=np.float64)] + [np.asarray(a, dtype=np.float64) for a in (y, rowarg) if a is not None]
+    shape = np.broadcast(*arrs).shape
+
+    def flat(a):
+        return None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape)).ravel()
+    f, y, rowarg = flat(f), flat(y), flat(rowarg)
+    out = np.empty(f.shape[0])
+    none = ctypes.c_void_p(None)
+    _check(dev.lib, dev.lib.rr_lik_eval(
+        dev.ctx, LIK_EVAL_IDS[what], int(lik), float(lik_param), none if y is None else y.ctypes.data_as(ctypes.c_void_p),
+        f.ctypes.data_as(ctypes.c_void_p), none if rowarg is None else rowarg.ctypes.data_as(ctypes.c_void_p), f.shape[0],
+        out.ctypes.data_as(ctypes.c_void_p)))
+    return out.reshape(shape)
 
 
 UPDATER_IDS = {"SGDUpdater": 0, "AdaDelta": 1, "AdaGrad": 2, "Momentum": 3, "Adam": 4}   # RR_UPD_*

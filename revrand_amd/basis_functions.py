@@ -940,6 +940,24 @@ class MinibatchFeatures(object):
             out[r0:r0 + chunk] = self.fm.project(Xc.shape[0], W)
         return out
 
+    def predictive(self, X, hypers, W, what, spec, y=None, quantile=None, p_lo=0.0, p_hi=0.0, chunk_rows=None):
+        """Per-row predictive statistics of the latent samples Phi(X) W under the likelihood `spec` = (id, scalar parameter,
+        per-row argument or None) (a likelihood's ``predictive_spec``), reduced on the device (FeatureMatrix.predictive): only
+        the (N, 2 | 3) result leaves the GPU.  Row chunks as in `project`; the per-row argument and `y` go with their rows."""
+        N = X.shape[0]
+        F = int(sum(int(b.get_dim(X)) for b in self.bases))
+        Fp = (F + 255) // 256 * 256
+        chunk = int(max(256, min(N, (8 << 30) // (8 * Fp)))) if chunk_rows is None else int(chunk_rows)
+        lik, lik_param, rowarg = spec
+        out = np.empty((N, 3 if what in ("logpdf", "cdf") else 2))
+        for r0 in range(0, N, chunk):
+            Xc = X[r0:r0 + chunk]
+            self.assemble(Xc, hypers)
+            out[r0:r0 + chunk] = self.fm.predictive(
+                Xc.shape[0], W, what, lik, lik_param, None if rowarg is None else rowarg[r0:r0 + chunk],
+                None if y is None else y[r0:r0 + chunk], quantile, p_lo, p_hi)
+        return out
+
     def release(self):
         if getattr(self, "resident", False):
             for k in self._kids:

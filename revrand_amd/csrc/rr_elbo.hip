@@ -3086,6 +3086,31 @@ int rr_featmat_glm_edphi(rr_featmat *fm, int64_t col0, int64_t ncols, double *E)
     return RR_OK;
 }
 
+// FSt (rows256, klp) = P W for a host (F, S) float64 matrix, queued on the context's stream: the sample matrix goes up zero
+// padded, P is transposed and one GEMM forms the latent samples of glm.py:572-620 (rr_featmat_project, rr_featmat_predictive)
+static int fm_project_gemm(rr_featmat *fm, const double *W, int S) {
+    rr_ctx *c = fm->ctx;
+    const int F = fm->F;
+    const int64_t sp = ((int64_t)S + 255) / 256 * 256, Fp = fm->ld;
+    const int64_t rows256 = (fm->rows + 255) / 256 * 256;
+    int rc = fm_glm_scratch(fm, sp, 1);
+    if (rc != RR_OK) return rc;
+    FmPass2 &s = *(FmPass2 *)fm->pass2;
+    const int64_t ldw = s.klp;
+    std::vector<float> w((size_t)Fp * ldw, 0.f);
+    for (int j = 0; j < F; ++j)
+        for (int i = 0; i < S; ++i) w[(size_t)j * ldw + i] = (float)W[(size_t)j * S + i];
+    RR_CHECK_HIP(hipStreamSynchronize(c->stream));
+    RR_CHECK_HIP(hipMemcpy(s.WSt, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(rr_transpose_f32_kernel, dim3((unsigned)(Fp / 64), (unsigned)(rows256 / 64)), dim3(256), 0, c->stream,
+                       fm->P, fm->rows, Fp, s.Pt, fm->max_rows);
+    fm->pt_rows = fm->rows;
+    rc = fm_gemm(c, s.Pt, fm->max_rows, s.WSt, ldw, s.FSt, ldw, Fp, rows256, ldw);
+    if (rc != RR_OK) return rc;
+    s.have_edphi = false;
+    return RR_OK;
+}
+
 int rr_featmat_project(rr_featmat *fm, const double *W, int S, double *out) {
     RR_REQUIRE(fm != nullptr && W != nullptr && out != nullptr && S >= 1 && S < (1 << 24), "rr_featmat_project: bad argument");
     RR_FM_REQUIRE_FILLED(fm, "rr_featmat_project");
@@ -3114,27 +3139,59 @@ int rr_featmat_project(rr_featmat *fm, const double *W, int S, double *out) {
         for (int64_t i = 0; i < fm->rows; ++i) out[i] = (double)h[i];
         return RR_OK;
     }
-    const int64_t sp = ((int64_t)S + 255) / 256 * 256, Fp = fm->ld;
-    const int64_t rows256 = (fm->rows + 255) / 256 * 256;
-    int rc = fm_glm_scratch(fm, sp, 1);
+    int rc = fm_project_gemm(fm, W, S);
     if (rc != RR_OK) return rc;
     FmPass2 &s = *(FmPass2 *)fm->pass2;
     const int64_t ldw = s.klp;
-    std::vector<float> w((size_t)Fp * ldw, 0.f);
-    for (int j = 0; j < F; ++j)
-        for (int i = 0; i < S; ++i) w[(size_t)j * ldw + i] = (float)W[(size_t)j * S + i];
-    RR_CHECK_HIP(hipStreamSynchronize(c->stream));
-    RR_CHECK_HIP(hipMemcpy(s.WSt, w.data(), w.size() * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(rr_transpose_f32_kernel, dim3((unsigned)(Fp / 64), (unsigned)(rows256 / 64)), dim3(256), 0, c->stream,
-                       fm->P, fm->rows, Fp, s.Pt, fm->max_rows);
-    fm->pt_rows = fm->rows;
-    rc = fm_gemm(c, s.Pt, fm->max_rows, s.WSt, ldw, s.FSt, ldw, Fp, rows256, ldw);
-    if (rc != RR_OK) return rc;
-    s.have_edphi = false;
     std::vector<float> h((size_t)fm->rows * S);
     RR_CHECK_HIP(hipStreamSynchronize(c->stream));
     RR_CHECK_HIP(hipMemcpy2D(h.data(), (size_t)S * 4, s.FSt, (size_t)ldw * 4, (size_t)S * 4, (size_t)fm->rows, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < h.size(); ++i) out[i] = (double)h[i];
+    return RR_OK;
+}
+
+int rr_featmat_predictive(rr_featmat *fm, const double *W, int S, int what, int lik, double lik_param, const double *rowarg,
+                          const double *yq, double p_lo, double p_hi, double *out) {
+    RR_REQUIRE(fm != nullptr && W != nullptr && out != nullptr && S >= 1 && S < (1 << 24), "rr_featmat_predictive: bad argument");
+    RR_REQUIRE(what >= RR_PRED_MOMENTS && what <= RR_PRED_INTERVAL, "rr_featmat_predictive: unknown statistic %d", what);
+    int rc = rr_predictive_check_lik("rr_featmat_predictive", lik, lik_param, rowarg);
+    if (rc != RR_OK) return rc;
+    RR_REQUIRE((what != RR_PRED_LOGPDF && what != RR_PRED_CDF) || yq != nullptr,
+               "rr_featmat_predictive: the log density needs its targets and the CDF its quantile");
+    RR_FM_REQUIRE_FILLED(fm, "rr_featmat_predictive");
+    if (fm->rows == 0) return RR_OK;
+    rr_ctx *c = fm->ctx;
+    RR_CHECK_HIP(hipSetDevice(c->device));
+    rc = fm_project_gemm(fm, W, S);   // (one sample included: the statistics are taken over FSt's columns)
+    if (rc != RR_OK) return rc;
+    FmPass2 &s = *(FmPass2 *)fm->pass2;
+    const int64_t rows = fm->rows;
+    const int oc = rr_predictive_out_cols(what);
+    // [out (rows, oc) | n (rows) | y (rows)] in one allocation of the call
+    double *d = nullptr;
+    RR_CHECK_HIP(hipMalloc((void **)&d, (size_t)rows * (oc + 2) * sizeof(double)));
+    double *dout = d, *dn = nullptr, *dy = nullptr;
+    hipError_t e = hipSuccess;
+    if (lik == RR_LIK_BINOMIAL) {
+        dn = d + rows * oc;
+        e = hipMemcpyAsync(dn, rowarg, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    }
+    if (e == hipSuccess && what == RR_PRED_LOGPDF) {
+        dy = d + rows * (oc + 1);
+        e = hipMemcpyAsync(dy, yq, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    }
+    if (e == hipSuccess) {
+        rc = rr_launch_predictive(c, s.FSt, rows, S, s.klp, what, lik, lik_param, dn, dy, what == RR_PRED_CDF ? yq[0] : 0.0, p_lo,
+                                  p_hi, dout);
+        if (rc == RR_OK) e = hipMemcpyAsync(out, dout, (size_t)rows * oc * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (also when the launch failed: the uploads above read host memory)
+    (void)hipFree(d);
+    if (rc != RR_OK) return rc;
+    if (e != hipSuccess) {
+        rr_set_error("rr_featmat_predictive failed: %s", hipGetErrorString(e));
+        return RR_ERR_HIP;
+    }
     return RR_OK;
 }
 

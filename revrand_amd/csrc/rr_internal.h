@@ -241,6 +241,13 @@ float *rr_fm_pass2_pt(void *p);  // FmPass2::Pt or null
 // what a child's gradient contraction outside rr_elbo.hip reads of the second pass' / GLM step's scratch (p may be null):
 // U = Phi C or EdPhi (ld of the matrix), err (rows), m32 (F); have_rows / have_edphi: which of the two U holds
 void rr_fm_pass2_views(void *p, float **U, float **err, float **m32, bool *have_rows, bool *have_edphi);
+// rr_predictive.hip: the reduction of the latent samples FSt (rows x ld float32, S valid columns) to RR_PRED_* statistics in
+// dout (rows x rr_predictive_out_cols(what) float64, device), queued on the context's stream; drowarg / dy: device float64
+// (binomial n / RR_PRED_LOGPDF targets) or null; q: the RR_PRED_CDF quantile
+int rr_launch_predictive(rr_ctx *c, const float *FSt, int64_t rows, int S, int64_t ld, int what, int lik, double lik_param,
+                         const double *drowarg, const double *dy, double q, double p_lo, double p_hi, double *dout);
+int rr_predictive_out_cols(int what);
+int rr_predictive_check_lik(const char *who, int lik, double lik_param, const void *rowarg);
 rr_ctx *rr_comm_ctx(rr_comm *comm);  // the context a communicator was bound to (rr_comm.hip)
 // Consumers of the feature matrix call this first: every column of [0, F) must have been put since rr_featmat_begin.
 #define RR_FM_REQUIRE_FILLED(fm, who)                                                                              \

@@ -125,11 +125,18 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         the listed GPUs, every member serves the rows of a minibatch that fall into its shard, and the step's Monte-Carlo
         sums are added over the members -- in HBM, with the optimiser's loop resident on every member (rr_glm_sgd_group_step),
         or on the host when the fit is one the device loops do not cover.  The minibatch stream, the draws and the optimiser
-        are the single-GPU run's; minibatches of fewer than 2048 rows per member are not split."""
+        are the single-GPU run's; minibatches of fewer than 2048 rows per member are not split.
+    predict_engine : "host" (default) | "device"
+        Where ``predict_moments``, ``predict``, ``predict_logpdf``, ``predict_cdf`` and ``predict_interval`` turn the latent
+        samples f = Phi w into their per-row results.  "host": the (N, nsamples) matrix comes back and the likelihood's
+        scipy functions run per sample.  "device": the likelihood's Ey / loglike / cdf, the reductions over the samples and
+        the quantile bisection run on the GPU in float64 (rr_featmat_predictive) and only the two or three numbers per row
+        come back; the likelihood must have a ``predictive_spec`` (TypeError otherwise -- never a host fallback).  The draws
+        are the same under both: ``randint`` then ``randn`` from ``random_``."""
 
     def __init__(self, likelihood=Gaussian(), basis=LinearBasis(), K=10, maxiter=3000, batch_size=10, updater=None,
                  nsamples=50, nstarts=500, random_state=None, sampler="host", distributed=False, gram_engine=None,
-                 devices=None):
+                 devices=None, predict_engine="host"):
         self.likelihood = likelihood
         self.basis = basis
         self.K = K
@@ -143,6 +150,7 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         self.distributed = distributed
         self.gram_engine = gram_engine  # arithmetic of the step's GEMMs (see StandardLinearModel); None = context setting
         self.devices = devices          # several GPUs behind this call, in this process (see StandardLinearModel; multigpu.py)
+        self.predict_engine = predict_engine
         self.random_ = check_random_state(self.random_state)
 
     def fit(self, X, y, likelihood_args=()):
@@ -164,6 +172,7 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
 
     def _fit(self, X, y, likelihood_args=()):
         X, y = check_X_y(X, y)
+        self._device_predictions()   # (validates predict_engine)
         self._drop_serving()
         self._dev_seed = None  # the device sampler is re-keyed from random_ per fit
         N, _ = X.shape
@@ -654,6 +663,9 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
 
     def predict_moments(self, X, nsamples=200, likelihood_args=()):
         """Monte-Carlo predictive mean and variance (glm.py:351-393)."""
+        if self._device_predictions():
+            out = self._predictive(X, nsamples, likelihood_args, "moments")
+            return out[:, 0].copy(), out[:, 1].copy()
         fs = self._sample_matrix(X, nsamples)                                 # N x nsamples
         Eyargs = tuple(chain(atleast_list(self.like_hypers_), likelihood_args))
         ys = np.empty(fs.shape)
@@ -666,6 +678,9 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
     def predict_logpdf(self, X, y, nsamples=200, likelihood_args=()):
         """Mean / min / max log predictive density over the latent samples (glm.py:395-444)."""
         X, y = check_X_y(X, y)
+        if self._device_predictions():
+            out = self._predictive(X, nsamples, likelihood_args, "logpdf", y=y)
+            return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
         fs = self._sample_matrix(X, nsamples)
         llargs = tuple(chain(atleast_list(self.like_hypers_), likelihood_args))
         ps = np.empty(fs.shape)
@@ -675,6 +690,9 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
 
     def predict_cdf(self, X, quantile, nsamples=200, likelihood_args=()):
         """Predictive CDF at `quantile` (glm.py:446-495)."""
+        if self._device_predictions():
+            out = self._predictive(X, nsamples, likelihood_args, "cdf", quantile=float(quantile))
+            return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
         fs = self._sample_matrix(X, nsamples)
         cdfarg = tuple(chain(atleast_list(self.like_hypers_), likelihood_args))
         ps = np.empty(fs.shape)
@@ -686,7 +704,12 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         """Central `percentile` interval of the predictive distribution, (lower, upper) per query row -- the quantiles
         of the CDF averaged over the latent samples (glm.py:497-570).  The reference root-finds row by row in a process
         pool; here every row is bisected at once on the (N, nsamples) sample matrix (`multiproc` is accepted and
-        ignored).  Same search bracket, and NaN where the bracket does not contain the quantile."""
+        ignored).  Same search bracket, and NaN where the bracket does not contain the quantile.  With
+        ``predict_engine="device"`` the same bisection runs on the GPU, a wave per row, both tails in one launch."""
+        if self._device_predictions():
+            tail = 0.5 * (1. - percentile)
+            out = self._predictive(X, nsamples, likelihood_args, "interval", p_lo=tail, p_hi=1. - tail)
+            return out[:, 0].copy(), out[:, 1].copy()
         fs = self._sample_matrix(X, nsamples)                                 # N x nsamples
         N = fs.shape[0]
         rowargs = [np.asarray(a, dtype=float).reshape(N, 1) for a in _reshape_likelihood_args(likelihood_args, N)
@@ -701,14 +724,30 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         tail = 0.5 * (1. - percentile)
         return _bisect_quantile(sampled_cdf, tail, reach), _bisect_quantile(sampled_cdf, 1. - tail, reach)
 
-    def _sample_matrix(self, X, nsamples):
-        """Latent function samples f = Phi w, (N, nsamples), the product on the device (glm.py:572-620)."""
+    def _device_predictions(self):
+        """True under predict_engine="device" (whose likelihood must name its device formulas), False under "host"."""
+        engine = getattr(self, "predict_engine", "host")
+        if engine == "host":
+            return False
+        if engine != "device":
+            raise ValueError("predict_engine must be 'host' or 'device'")
+        if not callable(getattr(self.likelihood, "predictive_spec", None)):
+            raise TypeError("predict_engine='device' needs a likelihood with a predictive_spec; {} has none"
+                            .format(type(self.likelihood).__name__))
+        return True
+
+    def _draw_weights(self, X, nsamples):
+        """(checked X, w (D, nsamples)): the posterior weight samples of a prediction call, drawn from `random_` in the
+        reference's order -- randint then randn (glm.py:606-610)."""
         check_is_fitted(self, ['weights_', 'covariance_', 'basis_hypers_', 'like_hypers_', 'regularizer_'])
         X = check_array(X)
         D, K = self.weights_.shape
         k = self.random_.randint(0, K, size=(nsamples,))
         w = self.weights_[:, k] + self.random_.randn(D, nsamples) * np.sqrt(self.covariance_[:, k])
-        # the feature matrix is kept between prediction calls (per process; dropped by fit and by pickling)
+        return X, w
+
+    def _serving(self):
+        """The feature matrix kept between prediction calls (per process; dropped by fit and by pickling)."""
         srv = self.__dict__.get("_serve_feats")
         if srv is None or srv[0] != os.getpid():
             g = self._group()
@@ -718,7 +757,20 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
             else:
                 served = MinibatchFeatures(self.basis)
             srv = self.__dict__["_serve_feats"] = (os.getpid(), served)
-        return srv[1].project(X, atleast_list(self.basis_hypers_), w)
+        return srv[1]
+
+    def _sample_matrix(self, X, nsamples):
+        """Latent function samples f = Phi w, (N, nsamples), the product on the device (glm.py:572-620)."""
+        X, w = self._draw_weights(X, nsamples)
+        return self._serving().project(X, atleast_list(self.basis_hypers_), w)
+
+    def _predictive(self, X, nsamples, likelihood_args, what, **kw):
+        """predict_engine="device": the (N, 2 | 3) per-row statistics of `what`, reduced over the latent samples on the GPU."""
+        X, w = self._draw_weights(X, nsamples)
+        N = X.shape[0]
+        largs = [a for a in _reshape_likelihood_args(likelihood_args, N) if len(a)]
+        spec = self.likelihood.predictive_spec(atleast_list(self.like_hypers_), largs, N)
+        return self._serving().predictive(X, atleast_list(self.basis_hypers_), w, what, spec, **kw)
 
     def _sample_func(self, X, nsamples, genaxis=1):
         """Generator over latent function samples, column-wise (genaxis=1) or per observation (genaxis=0)."""

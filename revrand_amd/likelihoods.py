@@ -58,6 +58,11 @@ class Bernoulli(object):
         per latent sample) for the fused SVI step."""
         return RR_LIK_BERNOULLI, 0.0, None, 0.0
 
+    def predictive_spec(self, lpars, largs, N):
+        """(likelihood id, scalar parameter, per-row argument (N,) or None) for the device's predictive statistics
+        (``GeneralizedLinearModel(predict_engine="device")``: rr_featmat_predictive)."""
+        return RR_LIK_BERNOULLI, 0.0, None
+
     def __repr__(self):
         return "{}()".format(type(self).__name__)
 
@@ -82,6 +87,12 @@ class Binomial(Bernoulli):
         n = np.broadcast_to(np.asarray(largs[0], dtype=float), np.shape(y))
         const = float((gammaln(n + 1) - gammaln(y + 1) - gammaln(n - y + 1)).sum())
         return RR_LIK_BINOMIAL, 0.0, n, const
+
+    def predictive_spec(self, lpars, largs, N):
+        if len(largs) != 1:
+            raise ValueError("the binomial likelihood takes one argument, the number of trials n")
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(largs[0], dtype=float).ravel(), (N,)))
+        return RR_LIK_BINOMIAL, 0.0, n
 
 
 class Gaussian(Bernoulli):
@@ -126,6 +137,9 @@ class Gaussian(Bernoulli):
     def device_spec(self, y, lpars, largs):
         var = float(self._check_param(lpars[0] if len(lpars) else None))
         return RR_LIK_GAUSSIAN, var, None, float(-0.5 * np.log(2 * np.pi * var) * np.size(y))
+
+    def predictive_spec(self, lpars, largs, N):
+        return RR_LIK_GAUSSIAN, float(self._check_param(lpars[0] if len(lpars) else None)), None
 
     def __repr__(self):
         return "{}(var={})".format(type(self).__name__, self.params)
@@ -178,6 +192,9 @@ class Poisson(Bernoulli):
     def device_spec(self, y, lpars, largs):
         lid = RR_LIK_POISSON_EXP if self.tranfcn == 'exp' else RR_LIK_POISSON_SOFTPLUS
         return lid, 0.0, None, -_sum_gammaln1p(y)
+
+    def predictive_spec(self, lpars, largs, N):
+        return (RR_LIK_POISSON_EXP if self.tranfcn == 'exp' else RR_LIK_POISSON_SOFTPLUS), 0.0, None
 
     def __repr__(self):
         return "{}(tranfcn='{}')".format(type(self).__name__, self.tranfcn)

@@ -495,6 +495,14 @@ class ShardedMinibatchFeatures(object):
         out = map_rows(self.group, X.shape[0], lambda i, s, e: (self.feats[i].project(X[s:e], hypers, W),), n=self.n_use)
         return out[0]
 
+    def predictive(self, X, hypers, W, what, spec, y=None, quantile=None, p_lo=0.0, p_hi=0.0, chunk_rows=None):
+        """`MinibatchFeatures.predictive`, rows sharded: per-row results, so the members' parts are concatenated."""
+        lik, lik_param, rowarg = spec
+        out = map_rows(self.group, X.shape[0], lambda i, s, e: (self.feats[i].predictive(
+            X[s:e], hypers, W, what, (lik, lik_param, None if rowarg is None else rowarg[s:e]), None if y is None else y[s:e],
+            quantile, p_lo, p_hi, chunk_rows),), n=self.n_use)
+        return out[0]
+
     def release(self):
         self.group.map(lambda i: self.feats[i].release(), members=range(self.n_use))
         self.resident = False
