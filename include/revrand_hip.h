@@ -445,13 +445,24 @@ typedef struct rr_glm_sgd rr_glm_sgd;
                                  of its chain: basis = that random Fourier basis (n frequencies), 4 n columns                        \
                                  [cos | sin](VX + mX) | [cos | sin](VX - mX) (the reference's column order is cos+, sin+, cos-, sin-:  \
                                  the same blocks), n_ls = 2 Xdim coordinates [mean | length scales]                                   */
+#define RR_SGD_CHILD_CENTRES 3 /* RadialBasis / SigmoidalBasis (basis_functions.py:616-815): basis = an rr_centres_create handle with  \
+                                 f32 compute on the matrix' context, Xdim <= 128; M columns, n_ls = 1 (isotropic) or Xdim length    \
+                                 scales.  Features from the length scales in HBM, the gradient's sums in n_ls slots of the step's  \
+                                 contraction buffer (all-reduced with the random Fourier children's by the group / dist steps)    */
+#define RR_SGD_CHILD_POLY 4    /* PolynomialBasis (basis_functions.py:496-576): onescol + d order columns, no parameters            */
 typedef struct rr_glm_sgd_child {
     int kind;        /* RR_SGD_CHILD_* */
-    rr_basis *basis; /* RFF, GM: the basis (same context as the feature matrix); else NULL */
-    int d;           /* LINEAR: columns of X */
-    int onescol;     /* LINEAR: 1 = a column of ones first */
-    int n_ls;        /* RFF: 1 or Xdim; LINEAR: 0; GM: 2 Xdim ([mean | length scales]) */
+    rr_basis *basis; /* RFF, GM, CENTRES: the basis (same context as the feature matrix); else NULL */
+    int d;           /* LINEAR, POLY: columns of X */
+    int onescol;     /* LINEAR: 1 = a column of ones first; POLY: include_bias */
+    int n_ls;        /* RFF, CENTRES: 1 or Xdim; LINEAR, POLY: 0; GM: 2 Xdim ([mean | length scales]) */
+    int order;       /* POLY: powers 1 .. order of every column (>= 0); in the struct's former tail padding: sizeof stays 32 */
 } rr_glm_sgd_child;
+#ifdef __cplusplus
+static_assert(sizeof(rr_glm_sgd_child) == 32, "rr_glm_sgd_child: `order` must sit in the former tail padding (ABI)");
+#else
+_Static_assert(sizeof(rr_glm_sgd_child) == 32, "rr_glm_sgd_child: `order` must sit in the former tail padding (ABI)");
+#endif
 /* fm: an (empty) feature matrix whose F columns the children fill in order; z0, lower, upper (float64) and is_log (bytes):
  * host vectors of 2 F K + n_children + n_lik + (all length scales) entries; upd_par: 4 doubles (unused ones ignored);
  * maxiter: steps at most. */
@@ -488,6 +499,8 @@ void rr_glm_sgd_destroy(rr_glm_sgd *s);
  * updater, -ELBO and |gradient| per step -- float64 throughout (draws are float32 values).  Same children, z layout, updaters
  * and likelihoods as rr_glm_sgd; rr_glm_svi_supported says whether a shape is in range (F K and minibatch x F small enough for
  * one CU's LDS).
+ * RR_SGD_CHILD_CENTRES and RR_SGD_CHILD_POLY children are NOT taken (rr_glm_svi_create: RR_ERR_INVALID): those fits run
+ * rr_glm_sgd_step at every minibatch size.
  * dX[c], x_dtype[c], ldx[c]: child c's RESIDENT rows of its columns of X (all N rows, device); dy / drowarg: targets and the
  * binomial's n for all N rows (device, dtype); dlconst: per row, the part of loglike that does not depend on f (device float64:
  * Poisson -lgamma(y + 1), binomial lgamma(n + 1) - lgamma(y + 1) - lgamma(n - y + 1); NULL: zero -- Bernoulli, Gaussian);

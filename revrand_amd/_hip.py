@@ -1181,13 +1181,28 @@ UPDATER_IDS = {"SGDUpdater": 0, "AdaDelta": 1, "AdaGrad": 2, "Momentum": 3, "Ada
 class SgdChild(ctypes.Structure):
     """rr_glm_sgd_child (include/revrand_hip.h)"""
     _fields_ = [("kind", ctypes.c_int), ("basis", ctypes.c_void_p), ("d", ctypes.c_int), ("onescol", ctypes.c_int),
-                ("n_ls", ctypes.c_int)]
+                ("n_ls", ctypes.c_int), ("order", ctypes.c_int)]   # (order: in the former tail padding -- 32 bytes as before)
+
+
+SGD_CHILD_KINDS = {"rff": 0, "linear": 1, "gm": 2, "centres": 3, "poly": 4}   # RR_SGD_CHILD_*
+
+
+def _fill_sgd_child(k, ch):
+    """One rr_glm_sgd_child from a child tuple of ResidentSgd; returns its number of basis parameters."""
+    k.kind, k.basis, k.d, k.onescol, k.n_ls, k.order = SGD_CHILD_KINDS[ch[0]], None, 0, 0, 0, 0
+    if ch[0] in ("rff", "gm", "centres"):   # gm: a spectral-mixture component on its dense handle, [mean | length scales]
+        k.basis, k.n_ls = ch[1].h, int(ch[2])
+    elif ch[0] == "poly":
+        k.d, k.onescol, k.order = int(ch[1]), 1 if ch[2] else 0, int(ch[3])
+    else:
+        k.d, k.onescol = int(ch[1]), 1 if ch[2] else 0
+    return k.n_ls
 
 
 class ResidentSgd(object):
     """The SVI loop with its parameters in HBM (rr_glm_sgd): `step` queues one whole SGD step and returns at once.
-    children: ("rff", RffHandle, n_ls) | ("gm", RffHandle of the chain's dense equivalent, 2 Xdim) | ("linear", d, onescol) in
-    concatenation order."""
+    children: ("rff", RffHandle, n_ls) | ("gm", RffHandle of the chain's dense equivalent, 2 Xdim) | ("linear", d, onescol) |
+    ("centres", CentresHandle, n_ls) | ("poly", d, include_bias, order) in concatenation order."""
 
     def __init__(self, fm, children, K, n_lik, z0, lower, upper, is_log, updater_id, updater_par, maxiter):
         self.fm, self.children, self.lib = fm, list(children), fm.lib      # (all kept alive for as long as the loop)
@@ -1198,11 +1213,7 @@ class ResidentSgd(object):
         kids = (SgdChild * len(self.children))()
         n_ls = 0
         for k, ch in zip(kids, self.children):
-            if ch[0] in ("rff", "gm"):   # gm: a spectral-mixture component on its dense handle, [mean | length scales]
-                k.kind, k.basis, k.d, k.onescol, k.n_ls = (0 if ch[0] == "rff" else 2), ch[1].h, 0, 0, int(ch[2])
-                n_ls += int(ch[2])
-            else:
-                k.kind, k.basis, k.d, k.onescol, k.n_ls = 1, None, int(ch[1]), 1 if ch[2] else 0, 0
+            n_ls += _fill_sgd_child(k, ch)
         self.nk = len(self.children)
         self.np_ = 2 * fm.F * K + self.nk + n_lik + n_ls
         if not (z0.shape == lower.shape == upper.shape == is_log.shape == (self.np_,)):
@@ -1268,7 +1279,8 @@ class SgdBatch(ctypes.Structure):
 
 class ResidentSgdGroup(object):
     """One ResidentSgd per member of a device group, stepped together (rr_glm_sgd_group_step): every member works on ITS rows of
-    the minibatch, the row sums are all-reduced in HBM, the members' copies of the parameters stay bit-identical."""
+    the minibatch, the row sums are all-reduced in HBM, the members' copies of the parameters stay bit-identical.  The members'
+    children are ResidentSgd's tuples -- "centres" and "poly" included: a centres child's sums ride the same all-reduce."""
 
     def __init__(self, comms, sgds):
         self.comms, self.sgds, self.n, self.lib = comms, list(sgds), len(sgds), sgds[0].lib
@@ -1308,7 +1320,8 @@ class ResidentSgdGroup(object):
 class FusedSvi(object):
     """The SVI loop for small minibatches, many steps per launch (rr_glm_svi, rr_svi.hip).
     children: ("rff", RffHandle, n_ls, dX) | ("linear", d, onescol, dX) in concatenation order, dX the child's RESIDENT
-    rows (DeviceMatrix, all N rows); dy / drowarg: DeviceBuffers of all N targets / per-row arguments."""
+    rows (DeviceMatrix, all N rows); dy / drowarg: DeviceBuffers of all N targets / per-row arguments.  ResidentSgd's "centres"
+    and "poly" tuples (+ dX) are passed on as they are and refused by the library: that kernel does not hold them."""
 
     def __init__(self, dev, children, N, dy, drowarg, dlconst, K, L, M, lik, n_lik, z0, lower, upper, is_log, updater_id, updater_par,
                  maxiter, bmag):
@@ -1323,14 +1336,11 @@ class FusedSvi(object):
         ptrs, dts, lds = (ctypes.c_void_p * nk)(), (ctypes.c_int * nk)(), (ctypes.c_int64 * nk)()
         F = n_ls = 0
         for i, (k, ch) in enumerate(zip(kids, self.children)):
-            dX = ch[3]
-            if ch[0] == "rff":
-                k.kind, k.basis, k.d, k.onescol, k.n_ls = 0, ch[1].h, 0, 0, int(ch[2])
-                n_ls += int(ch[2])
-                F += 2 * ch[1].n
-            else:
-                k.kind, k.basis, k.d, k.onescol, k.n_ls = 1, None, int(ch[1]), 1 if ch[2] else 0, 0
-                F += int(ch[1]) + (1 if ch[2] else 0)
+            dX = ch[-1]
+            n_ls += _fill_sgd_child(k, ch[:-1])
+            F += {"rff": lambda: 2 * ch[1].n, "gm": lambda: 4 * ch[1].n, "centres": lambda: ch[1].M,
+                  "poly": lambda: (1 if ch[2] else 0) + int(ch[1]) * int(ch[3]),
+                  "linear": lambda: int(ch[1]) + (1 if ch[2] else 0)}[ch[0]]()
             p = dX.ptr
             ptrs[i] = p if isinstance(p, int) else p.value
             dts[i], lds[i] = rr_dtype(dX.dtype), dX.ld

@@ -1528,17 +1528,6 @@ class FastFoodGM(FastFoodRBF):
 # Polynomial and centre bases (reference: basis_functions.py:496-576, 616-815)
 # --------------------------------------------------------------------------------------
 
-def _in_device_group(basis=None):
-    """True on a member thread of a device group (`_hip.device_scope`): sharded multi-GPU fits do not cover the bases below,
-    which then decline their resident routes -- and say so (multigpu.ShardedFitState.make logs that one GPU is used; a
-    minibatch assembled on a member takes the generic child: the basis' `transform` output, uploaded)."""
-    inside = getattr(_hip._tls, "dev", None) is not None
-    if inside and basis is not None:
-        log.info("%s: no device-resident child inside a device group (devices=...); its transform output is uploaded instead",
-                 type(basis).__name__)
-    return inside
-
-
 class PolynomialBasis(Basis):
     """[1, X^1, ..., X^order] (basis_functions.py:496-576): an optional bias column, then for every input dimension i its
     powers x_i^1 .. x_i^order next to each other (column ``bias + i * order + p - 1``).  No hyper-parameters.  ``transform``
@@ -1577,9 +1566,9 @@ class PolynomialBasis(Basis):
 
     @slice_transform
     def _resident_child(self, X, dtype=None):
-        if dtype == "f64" or self._width(X.shape[1]) == 0 or _in_device_group(self):
+        if dtype == "f64" or self._width(X.shape[1]) == 0:
             return None
-        return _ResidentPoly(self, X)
+        return _ResidentPoly(self, X)   # (on the calling thread's device: a member's inside a device group)
 
     def __repr__(self):
         return "{}(order={}, include_bias={}, regularizer={})".format(type(self).__name__, self.order, self.include_bias,
@@ -1648,9 +1637,9 @@ class RadialBasis(_LengthScaleBasis):
 
     def _make_child(self, X, dtype):
         # the float64 feature matrix is not extended to these bases, nor are inputs wider than the centre tile's LDS budget
-        if dtype == "f64" or self.dtype != "f32" or X.shape[1] != self.d or self.d > 128 or _in_device_group(self):
+        if dtype == "f64" or self.dtype != "f32" or X.shape[1] != self.d or self.d > 128:
             return None
-        return _ResidentCentres(self, X)
+        return _ResidentCentres(self, X)   # (handle and rows on the calling thread's device: a member's inside a device group)
 
     @slice_transform
     def _resident_child(self, X, dtype=None):

@@ -260,6 +260,21 @@ rr_poly_features_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d,
     }
 }
 
+// ---- the resident SVI loop's side (rr_glm_sgd, rr_elbo.hip) --------------------------------------------------------
+// The d float32 feature scales of centres_prepare from the child's float64 length scales in HBM (the loop's x, after
+// rr_glm_sgd_from_log_kernel): the same clamp and isotropic broadcast, into a buffer the LOOP owns.  A zero length scale gives
+// the clamped +-1e18, a NaN stays a NaN: nothing can be refused from inside a queued step.
+__global__ void __launch_bounds__(128)
+rr_centres_scale_dev_kernel(const double *__restrict__ ls, int n_ls, int d, int radial, float *__restrict__ scale) {
+#pragma clang fp contract(off)
+    const int i = (int)blockIdx.x * 128 + (int)threadIdx.x;
+    if (i >= d) return;
+    const double l = ls[n_ls == 1 ? 0 : i];
+    const double s = radial ? 1.0 / (2.0 * l * l) : 1.0 / l;
+    const double lim = 1e18;
+    scale[i] = (float)(s > lim ? lim : (s < -lim ? -lim : s));
+}
+
 CentresData *centres_of(rr_basis *b) { return b != nullptr && b->kind == RR_KIND_CENTRES ? (CentresData *)b->centres : nullptr; }
 
 // The per-dimension factors for these length scales, cached like rr_basis_prepare caches the scaled W
@@ -371,35 +386,15 @@ int centres_host_call(rr_basis *b, const void *X, int x_dtype, int64_t N, int64_
     return rc;
 }
 
+// the contraction's launch and its second stage: dg[i] += gfac.g[i] * (the block sums in index order), i < nd
 template <bool SLM>
-int centres_contract(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, double *dg,
-                     const char *who) {
-    CentresData *cd = centres_of(b);
-    RR_REQUIRE(fm != nullptr && cd != nullptr && dg != nullptr, "%s: bad argument", who);
+int centres_contract_launch(rr_featmat *fm, CentresData *cd, const void *dX, int x_dtype, int64_t ldx, int64_t col0, int nd,
+                            const GfacArgs &gfac, double *dg) {
     float *U = nullptr, *err = nullptr, *m32 = nullptr;
     bool have_rows = false, have_edphi = false;
     rr_fm_pass2_views(fm->pass2, &U, &err, &m32, &have_rows, &have_edphi);
-    RR_REQUIRE(SLM ? have_rows : have_edphi, "%s: call %s first", who, SLM ? "rr_featmat_pass2_rows" : "rr_featmat_glm_step");
-    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "%s: bad dtype", who);
-    RR_REQUIRE(b->d <= 128, "%s: needs d <= 128, got %d", who, b->d);
-    RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "%s: columns out of range", who);
-    RR_REQUIRE(ldx >= b->d, "%s: device X needs ldx >= d = %d", who, b->d);
-    const std::vector<double> *put_ls = nullptr;
-    for (const auto &pc : fm->centres_puts)
-        if (pc.basis == b && pc.col0 == col0) put_ls = &pc.ls;
-    RR_REQUIRE(put_ls != nullptr, "%s: this basis was not put at column %lld since rr_featmat_begin (rr_featmat_put_centres)", who,
-               (long long)col0);
-    if (fm->rows == 0) return RR_OK;
-    RR_REQUIRE(dX != nullptr, "%s: null X", who);
     rr_ctx *c = fm->ctx;
     RR_CHECK_HIP(hipSetDevice(c->device));
-    const int nd = (int)put_ls->size();
-    GfacArgs gfac;
-    for (int i = 0; i < 128; ++i) {
-        const double l = i < nd ? (*put_ls)[(size_t)i] : 1.0;
-        const double g = cd->kind == RR_CENTRES_RADIAL ? 1.0 / (l * l * l) : 1.0 / (l * l);
-        gfac.g[i] = cd->kind == RR_CENTRES_RADIAL ? g * g : g;
-    }
     int DP = 1;
     while (DP < nd) DP *= 2;
     const int ctiles = (cd->M + CT - 1) / CT;
@@ -428,6 +423,57 @@ int centres_contract(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, i
     return rr_det_reduce(c, (const double *)part, nblocks, nd, nd, dg);
 }
 
+template <bool SLM>
+int centres_contract(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, double *dg,
+                     const char *who) {
+    CentresData *cd = centres_of(b);
+    RR_REQUIRE(fm != nullptr && cd != nullptr && dg != nullptr, "%s: bad argument", who);
+    float *U = nullptr, *err = nullptr, *m32 = nullptr;
+    bool have_rows = false, have_edphi = false;
+    rr_fm_pass2_views(fm->pass2, &U, &err, &m32, &have_rows, &have_edphi);
+    RR_REQUIRE(SLM ? have_rows : have_edphi, "%s: call %s first", who, SLM ? "rr_featmat_pass2_rows" : "rr_featmat_glm_step");
+    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "%s: bad dtype", who);
+    RR_REQUIRE(b->d <= 128, "%s: needs d <= 128, got %d", who, b->d);
+    RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "%s: columns out of range", who);
+    RR_REQUIRE(ldx >= b->d, "%s: device X needs ldx >= d = %d", who, b->d);
+    const std::vector<double> *put_ls = nullptr;
+    for (const auto &pc : fm->centres_puts)
+        if (pc.basis == b && pc.col0 == col0) put_ls = &pc.ls;
+    RR_REQUIRE(put_ls != nullptr, "%s: this basis was not put at column %lld since rr_featmat_begin (rr_featmat_put_centres)", who,
+               (long long)col0);
+    if (fm->rows == 0) return RR_OK;
+    RR_REQUIRE(dX != nullptr, "%s: null X", who);
+    const int nd = (int)put_ls->size();
+    GfacArgs gfac;
+    for (int i = 0; i < 128; ++i) {
+        const double l = i < nd ? (*put_ls)[(size_t)i] : 1.0;
+        const double g = cd->kind == RR_CENTRES_RADIAL ? 1.0 / (l * l * l) : 1.0 / (l * l);
+        gfac.g[i] = cd->kind == RR_CENTRES_RADIAL ? g * g : g;
+    }
+    return centres_contract_launch<SLM>(fm, cd, dX, x_dtype, ldx, col0, nd, gfac, dg);
+}
+
+// features of fm's rows at col0 with the d float32 scales at `scale` (device), on the context's stream
+void centres_launch_features(rr_featmat *fm, const CentresData *cd, int d, const void *dX, int x_dtype, int64_t ldx,
+                             const float *scale, int64_t col0) {
+    const int a = (int)(col0 & 3);
+    const int rpb = 256;
+    const dim3 grid((unsigned)((fm->rows + rpb - 1) / rpb), (unsigned)((a + cd->M + CT - 1) / CT));
+    const size_t lds = ((size_t)d * CT + (size_t)((d + 3) & ~3) + (size_t)RT * (d + 1)) * 4;
+    float *Pa = fm->P + (col0 - a);
+#define RR_CF(TX, KIND)                                                                                                        \
+    hipLaunchKernelGGL((rr_centres_features_kernel<TX, KIND>), grid, dim3(256), lds, fm->ctx->stream, (const TX *)dX, fm->rows, ldx, d, \
+                       cd->Ct32, cd->Mp, cd->M, scale, Pa, fm->ld, a, rpb)
+    if (cd->kind == RR_CENTRES_RADIAL) {
+        if (x_dtype == RR_F32) RR_CF(float, RR_CENTRES_RADIAL);
+        else RR_CF(double, RR_CENTRES_RADIAL);
+    } else {
+        if (x_dtype == RR_F32) RR_CF(float, RR_CENTRES_SIGMOID);
+        else RR_CF(double, RR_CENTRES_SIGMOID);
+    }
+#undef RR_CF
+}
+
 }  // namespace
 
 void rr_centres_data_free(void *p) {
@@ -437,6 +483,63 @@ void rr_centres_data_free(void *p) {
     for (void *x : q)
         if (x) (void)hipFree(x);
     delete cd;
+}
+
+// ---- what the resident SVI loop (rr_elbo.hip) calls: length scales in HBM, no host copy -------------------------------
+// (no synchronisation in the steady state: the contraction's block partials use the context's grow-only rr_det_scratch,
+// which waits for the stream once when it has to grow -- the first step, or a larger minibatch)
+// RR_OK when b can be a RR_SGD_CHILD_CENTRES child of a loop on `ctx` with n_ls length scales; *M its width, *radial its kind
+bool rr_centres_loop_child(const rr_basis *b, const rr_ctx *ctx, int n_ls, int *M, int *radial) {
+    if (b == nullptr || b->kind != RR_KIND_CENTRES || b->centres == nullptr || b->compute != RR_F32 || b->ctx != ctx || b->d > 128 ||
+        !(n_ls == 1 || n_ls == b->d))
+        return false;
+    const CentresData *cd = (const CentresData *)b->centres;
+    *M = cd->M;
+    *radial = cd->kind == RR_CENTRES_RADIAL ? 1 : 0;
+    return true;
+}
+
+// rr_featmat_put_centres with the n_ls float64 length scales at dls (device): their float32 scales go to dscale (d floats
+// the CALLER owns -- neither the handle's cache nor a centres_puts record is touched), then the feature kernel reads them
+int rr_fm_put_centres_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *dls, int n_ls,
+                          float *dscale, int64_t col0) {
+    CentresData *cd = centres_of(b);
+    RR_REQUIRE(fm != nullptr && cd != nullptr && dls != nullptr && dscale != nullptr, "rr_fm_put_centres_dev: bad argument");
+    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_fm_put_centres_dev: bad dtype");
+    RR_REQUIRE(b->d <= 128 && (n_ls == 1 || n_ls == b->d), "rr_fm_put_centres_dev: needs d <= 128 and 1 or d length scales");
+    RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "rr_fm_put_centres_dev: columns out of range");
+    RR_REQUIRE(ldx >= b->d, "rr_fm_put_centres_dev: device X needs ldx >= d = %d", b->d);
+    if (fm->rows == 0) return RR_OK;
+    RR_REQUIRE(dX != nullptr, "rr_fm_put_centres_dev: null X");
+    RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
+    const int rc = rr_fm_claim(fm, col0, cd->M, "rr_fm_put_centres_dev");
+    if (rc != RR_OK) return rc;
+    hipLaunchKernelGGL(rr_centres_scale_dev_kernel, dim3(1), dim3(128), 0, fm->ctx->stream, dls, n_ls, b->d,
+                       cd->kind == RR_CENTRES_RADIAL ? 1 : 0, dscale);
+    centres_launch_features(fm, cd, b->d, dX, x_dtype, ldx, dscale, col0);
+    RR_CHECK_HIP(hipGetLastError());
+    return RR_OK;
+}
+
+// dS[i] += S_i, i < n_ls: the GLM step's contraction with UNIT factors -- sum E Phi (x_i - c_i)^2 (radial) or
+// sum -E Phi (1 - Phi) |x_i - c_i| (sigmoid) over the matrix' rows against the EdPhi the step stored, dS in device memory;
+// what is left of the gradient (1 / l^6 or 1 / l^2, the sign) is the update kernel's, from the length scales in HBM
+int rr_fm_glm_centres_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, int n_ls, double *dS) {
+    CentresData *cd = centres_of(b);
+    RR_REQUIRE(fm != nullptr && cd != nullptr && dS != nullptr, "rr_fm_glm_centres_dev: bad argument");
+    float *U = nullptr, *err = nullptr, *m32 = nullptr;
+    bool have_rows = false, have_edphi = false;
+    rr_fm_pass2_views(fm->pass2, &U, &err, &m32, &have_rows, &have_edphi);
+    RR_REQUIRE(have_edphi, "rr_fm_glm_centres_dev: the step did not store EdPhi");
+    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_fm_glm_centres_dev: bad dtype");
+    RR_REQUIRE(b->d <= 128 && (n_ls == 1 || n_ls == b->d), "rr_fm_glm_centres_dev: needs d <= 128 and 1 or d length scales");
+    RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "rr_fm_glm_centres_dev: columns out of range");
+    RR_REQUIRE(ldx >= b->d, "rr_fm_glm_centres_dev: device X needs ldx >= d = %d", b->d);
+    if (fm->rows == 0) return RR_OK;
+    RR_REQUIRE(dX != nullptr, "rr_fm_glm_centres_dev: null X");
+    GfacArgs gfac;
+    for (int i = 0; i < 128; ++i) gfac.g[i] = 1.0;
+    return centres_contract_launch<false>(fm, cd, dX, x_dtype, ldx, col0, n_ls, gfac, dS);
 }
 
 extern "C" {
@@ -508,22 +611,7 @@ int rr_featmat_put_centres(rr_featmat *fm, rr_basis *b, const void *dX, int x_dt
     if (rc != RR_OK) return rc;
     fm->centres_puts.push_back({b, col0, std::vector<double>(lenscale, lenscale + n_ls)});  // for the contractions
     // (the P^T side copy is not written: pt_covered stays, so consumers run their transposing pass)
-    const int a = (int)(col0 & 3), d = b->d;
-    const int rpb = 256;
-    const dim3 grid((unsigned)((fm->rows + rpb - 1) / rpb), (unsigned)((a + cd->M + CT - 1) / CT));
-    const size_t lds = ((size_t)d * CT + (size_t)((d + 3) & ~3) + (size_t)RT * (d + 1)) * 4;
-    float *Pa = fm->P + (col0 - a);
-#define RR_CF(TX, KIND)                                                                                                        \
-    hipLaunchKernelGGL((rr_centres_features_kernel<TX, KIND>), grid, dim3(256), lds, fm->ctx->stream, (const TX *)dX, fm->rows, ldx, d, \
-                       cd->Ct32, cd->Mp, cd->M, cd->scale32, Pa, fm->ld, a, rpb)
-    if (cd->kind == RR_CENTRES_RADIAL) {
-        if (x_dtype == RR_F32) RR_CF(float, RR_CENTRES_RADIAL);
-        else RR_CF(double, RR_CENTRES_RADIAL);
-    } else {
-        if (x_dtype == RR_F32) RR_CF(float, RR_CENTRES_SIGMOID);
-        else RR_CF(double, RR_CENTRES_SIGMOID);
-    }
-#undef RR_CF
+    centres_launch_features(fm, cd, b->d, dX, x_dtype, ldx, cd->scale32, col0);
     RR_CHECK_HIP(hipGetLastError());
     return RR_OK;
 }

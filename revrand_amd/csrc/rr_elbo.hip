@@ -3235,7 +3235,10 @@ struct rr_glm_sgd {
     rr_featmat *fm = nullptr;
     std::vector<rr_glm_sgd_child> kids;
     std::vector<int> col0, width, ls0;  // per child: first column, columns, first length-scale coordinate (relative to the ls block)
-    std::vector<double *> dTk;          // per child (random Fourier): its (d, n) contraction inside dT
+    std::vector<double *> dTk;          // per child (random Fourier): its (d, n) contraction inside dT; (centres): its n_ls sums S_i
+    std::vector<int> radial;            // per child (centres): 1 = RadialBasis, 0 = SigmoidalBasis
+    float *cscale = nullptr;            // per child and step parity, 128 floats: a centres child's feature scales for the step's
+                                        //   length scales (rr_fm_put_centres_dev) -- the loop's own, never the handle's cache
     int nkids = 0, K = 0, F = 0, n_ls = 0, n_lik = 0, updater = 0, n_h = 0;
     int64_t fk = 0, np = 0, maxiter = 0, t = 0, dT_count = 0;
     double up[4] = {0, 0, 0, 0};
@@ -3433,7 +3436,9 @@ struct SgdUpdArgs {
     const double *x, *red, *Edm, *EdC, *aux, *lower, *upper;
     const unsigned char *islog;
     const int *slice_of_f, *slice_lo, *slice_hi, *h_of_ls;
-    const unsigned char *ls_plain = nullptr;  // per basis parameter: 1 = its gradient is the sum itself (a mixture's mean), 0 = / l^2
+    // per basis parameter: 1 = its gradient is the sum itself (a mixture's mean), 0 = / l^2 (random Fourier, mixture and
+    // sigmoid-centre length scales), 2 = * (1 / l^3)^2 (a radial-centre length scale: rr_centres.hip's gfac)
+    const unsigned char *ls_plain = nullptr;
     double *z, *s1, *s2, *npart;
     int F, K, nkids, n_lik, n_ls, updater, L;
     int64_t np, p0, p1;  // all coordinates; this launch's are [p0, p1)
@@ -3496,7 +3501,11 @@ __global__ void __launch_bounds__(256) rr_glm_sgd_update_kernel(const SgdUpdArgs
             const int j = (int)(p - (2 * fk + a.nkids + a.n_lik));
             const double l = a.x[p];
             g = a.red[K * K + a.nkids + a.h_of_ls[j]];
-            if (!(a.ls_plain && a.ls_plain[j])) g = g / (1.0 * (l * l));
+            const int plain = a.ls_plain ? a.ls_plain[j] : 0;
+            if (plain == 2) {  // -S_i / l^6, the factor formed as centres_contract forms it
+                const double gi = 1.0 / (l * l * l);
+                g = g * (gi * gi);
+            } else if (!plain) g = g / (1.0 * (l * l));
         }
         if (a.islog[p]) g *= a.x[p];  // d/dz through x = exp(z)
     }
@@ -3580,7 +3589,7 @@ rr_glm_sgd_finish_kernel(const double *__restrict__ x, const double *__restrict_
 
 static void sgd_free(rr_glm_sgd *o) {
     void *q[] = {o->z, o->x, o->s1, o->s2, o->lower, o->upper, o->islog, o->red, o->npart, o->objs, o->norms, o->dT,
-                 o->slice_of_f, o->slice_lo, o->slice_hi, o->h_of_ls, o->hrows, o->ls_plain};
+                 o->slice_of_f, o->slice_lo, o->slice_hi, o->h_of_ls, o->hrows, o->ls_plain, o->cscale};
     for (void *v : q)
         if (v) (void)hipFree(v);
     for (hipEvent_t e : {o->ev[0], o->ev[1], o->e_ls[0], o->e_ls[1], o->e_feat[0], o->e_feat[1], o->e_in})
@@ -3616,7 +3625,7 @@ int rr_glm_sgd_create(rr_featmat *fm, int n_children, const rr_glm_sgd_child *ch
     int64_t dT_count = 0;
     for (int s = 0; s < n_children; ++s) {
         const rr_glm_sgd_child &k = children[s];
-        int w = 0;
+        int w = 0, is_radial = 0;
         if (k.kind == RR_SGD_CHILD_RFF) {
             rr_basis *b = k.basis;
             if (!(b != nullptr && b->kind == RR_KIND_RFF && !b->large && b->d <= 128 && b->ctx == fm->ctx &&
@@ -3645,6 +3654,26 @@ int rr_glm_sgd_create(rr_featmat *fm, int n_children, const rr_glm_sgd_child *ch
                 return RR_ERR_INVALID;
             }
             w = k.d + (k.onescol ? 1 : 0);
+        } else if (k.kind == RR_SGD_CHILD_CENTRES) {
+            int M = 0, radial = 0;
+            if (!rr_centres_loop_child(k.basis, fm->ctx, k.n_ls, &M, &radial)) {
+                delete o;
+                rr_set_error("rr_glm_sgd_create: child %d must be a centres basis (rr_centres_create) with f32 compute and Xdim <= 128 on "
+                             "the matrix' context with 1 or Xdim length scales", s);
+                return RR_ERR_INVALID;
+            }
+            w = M;
+            is_radial = radial;
+            dT_count += k.n_ls;
+        } else if (k.kind == RR_SGD_CHILD_POLY) {
+            if (!(k.d >= 1 && k.order >= 0 && k.n_ls == 0 && (int64_t)(k.onescol ? 1 : 0) + (int64_t)k.d * k.order >= 1 &&
+                  (int64_t)k.d * k.order < ((int64_t)1 << 30))) {
+                delete o;
+                rr_set_error("rr_glm_sgd_create: child %d: a polynomial child has d >= 1 columns of X, order >= 0, at least one column "
+                             "of its own and no length scale", s);
+                return RR_ERR_INVALID;
+            }
+            w = (k.onescol ? 1 : 0) + k.d * k.order;
         } else {
             delete o;
             rr_set_error("rr_glm_sgd_create: child %d: unknown kind %d", s, k.kind);
@@ -3659,6 +3688,7 @@ int rr_glm_sgd_create(rr_featmat *fm, int n_children, const rr_glm_sgd_child *ch
         o->col0.push_back(col);
         o->width.push_back(w);
         o->ls0.push_back(nls);
+        o->radial.push_back(is_radial);
         h_lo.push_back(col);
         h_hi.push_back(col + w);
         for (int f = col; f < col + w; ++f) h_slice[f] = s;
@@ -3700,6 +3730,7 @@ int rr_glm_sgd_create(rr_featmat *fm, int n_children, const rr_glm_sgd_child *ch
     if (e == hipSuccess) e = hipMalloc((void **)&o->h_of_ls, (size_t)(nls > 0 ? nls : 1) * sizeof(int));
     if (e == hipSuccess) e = hipMalloc((void **)&o->hrows, (size_t)(nls > 0 ? nls : 1) * sizeof(SgdHRow));
     if (e == hipSuccess) e = hipMalloc((void **)&o->ls_plain, (size_t)(nls > 0 ? nls : 1));
+    if (e == hipSuccess) e = hipMalloc((void **)&o->cscale, (size_t)n_children * 2 * 128 * sizeof(float));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&o->ev[0], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&o->ev[1], hipEventDisableTiming);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
@@ -3727,6 +3758,20 @@ int rr_glm_sgd_create(rr_featmat *fm, int n_children, const rr_glm_sgd_child *ch
     for (int s = 0; s < n_children; ++s) {
         const rr_glm_sgd_child &k = o->kids[(size_t)s];
         o->dTk.push_back(nullptr);
+        if (k.kind == RR_SGD_CHILD_CENTRES) {
+            // a centres length scale: ONE number of dT, the step's raw sum S_i (rr_fm_glm_centres_dev); g = -S_i / l^6 (radial)
+            // or -S_i / l^2 (sigmoid) -- _ResidentCentres.dhyp(var = 1); isotropic: input dimension 0's sum alone
+            o->dTk.back() = dTp;
+            for (int i = 0; i < k.n_ls; ++i) {
+                h_of_ls.push_back((int)hrows.size());
+                h_plain.push_back(o->radial[(size_t)s] ? 2 : 0);
+                SgdHRow r{dTp + i, nullptr, 1};
+                r.c1 = -1.0;
+                hrows.push_back(r);
+            }
+            dTp += k.n_ls;
+            continue;
+        }
         if (k.kind != RR_SGD_CHILD_RFF && k.kind != RR_SGD_CHILD_GM) continue;
         const int rcw = rr_basis_raw_w(k.basis);
         if (rcw != RR_OK) {
@@ -3893,7 +3938,14 @@ static int sgd_step_front(rr_glm_sgd *o, const SgdStepIn &in) {
                 rc = rr_fm_put_rff_dev(fm, k.basis, in.dX[s], in.x_dtype[s], in.ldx[s], ls, k.basis->d, o->col0[(size_t)s], mean, 1.0);
                 if (rc == RR_OK)
                     rc = rr_fm_put_rff_dev(fm, k.basis, in.dX[s], in.x_dtype[s], in.ldx[s], ls, k.basis->d, o->col0[(size_t)s] + 2 * k.basis->n, mean, -1.0);
-            } else rc = rr_featmat_put_linear(fm, in.dX[s], in.x_dtype[s], in.ldx[s], k.d, k.onescol, o->col0[(size_t)s]);
+            } else if (k.kind == RR_SGD_CHILD_CENTRES) {
+                // (the scales of step t + 1 are made on THIS stream right before the kernel that reads them, in a buffer of the
+                // step's parity: step t's contraction and update on the other stream read neither)
+                rc = rr_fm_put_centres_dev(fm, k.basis, in.dX[s], in.x_dtype[s], in.ldx[s], xls + o->ls0[(size_t)s], k.n_ls,
+                                           o->cscale + ((size_t)s * 2 + (size_t)par) * 128, o->col0[(size_t)s]);
+            } else if (k.kind == RR_SGD_CHILD_POLY)
+                rc = rr_featmat_put_poly(fm, in.dX[s], in.x_dtype[s], in.ldx[s], k.d, k.order, k.onescol, o->col0[(size_t)s]);
+            else rc = rr_featmat_put_linear(fm, in.dX[s], in.x_dtype[s], in.ldx[s], k.d, k.onescol, o->col0[(size_t)s]);
         }
     }
     if (rc != RR_OK) return rc;
@@ -3931,7 +3983,9 @@ static int sgd_step_front(rr_glm_sgd *o, const SgdStepIn &in) {
             if (rc == RR_OK)
                 rc = rr_featmat_glm_rff(fm, b, in.dX[ch], in.x_dtype[ch], in.ldx[ch], o->col0[(size_t)ch] + 2 * b->n,
                                         o->dTk[(size_t)ch] + (int64_t)b->d * b->n);
-        }
+        } else if (o->kids[(size_t)ch].kind == RR_SGD_CHILD_CENTRES)  // the raw sums S_i against the stored EdPhi, into the child's slots of dT
+            rc = rr_fm_glm_centres_dev(fm, o->kids[(size_t)ch].basis, in.dX[ch], in.x_dtype[ch], in.ldx[ch], o->col0[(size_t)ch],
+                                       o->kids[(size_t)ch].n_ls, o->dTk[(size_t)ch]);
     return rc;
 }
 

@@ -236,6 +236,12 @@ int rr_fm_claim(rr_featmat *fm, int64_t col0, int64_t width, const char *who);  
 // rr_featmat_put_rff with the length scales in device memory (rr_featmat.hip; the resident SVI loop of rr_elbo.hip)
 int rr_fm_put_rff_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *dls, int n_ls,
                       int64_t col0, const double *dshift = nullptr, double sgn = 0.0);
+// RadialBasis / SigmoidalBasis children of the resident SVI loop (rr_centres.hip): whether b can be one; its features from
+// length scales in device memory through a scale buffer the caller owns; the raw sums S_i of its length scales' gradient
+bool rr_centres_loop_child(const rr_basis *b, const rr_ctx *ctx, int n_ls, int *M, int *radial);
+int rr_fm_put_centres_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *dls, int n_ls,
+                          float *dscale, int64_t col0);
+int rr_fm_glm_centres_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, int n_ls, double *dS);
 void rr_fm_pass2_free(void *p);
 float *rr_fm_pass2_pt(void *p);  // FmPass2::Pt or null
 // what a child's gradient contraction outside rr_elbo.hip reads of the second pass' / GLM step's scratch (p may be null):

@@ -925,6 +925,11 @@ int rr_glm_svi_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *child
         } else {
             ok = false;
         }
+        if (k.kind == RR_SGD_CHILD_CENTRES || k.kind == RR_SGD_CHILD_POLY) {  // (rr_glm_sgd_step's kinds only)
+            svi_free(o);
+            rr_set_error("rr_glm_svi_create: child %d: centre and polynomial children (kind %d) are not taken by the fused loop", s, k.kind);
+            return RR_ERR_INVALID;
+        }
         if (!ok) {
             svi_free(o);
             rr_set_error("rr_glm_svi_create: child %d: a random Fourier basis of this context with 1 or Xdim length scales, or a "

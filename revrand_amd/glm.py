@@ -132,11 +132,19 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         scipy functions run per sample.  "device": the likelihood's Ey / loglike / cdf, the reductions over the samples and
         the quantile bisection run on the GPU in float64 (rr_featmat_predictive) and only the two or three numbers per row
         come back; the likelihood must have a ``predictive_spec`` (TypeError otherwise -- never a host fallback).  The draws
-        are the same under both: ``randint`` then ``randn`` from ``random_``."""
+        are the same under both: ``randint`` then ``randn`` from ``random_``.
+    resident_bases : "fourier" (default) | "all"
+        Which children let ``fit`` run its optimiser loop on the device (rr_glm_sgd_step and, with ``devices=`` or
+        ``distributed=True`` over RCCL, its group / rank forms).  "fourier": random Fourier, FastFood and linear children, as
+        before -- one RadialBasis, SigmoidalBasis or PolynomialBasis child keeps the host loop around ``_elbo``.  "all": those
+        three as well (float32 bases of Xdim <= 128 with a scalar or (d,) length scale): their features come from the length
+        scales in HBM and their gradient's sums are reduced there.  Such a fit takes the step-per-call loop at every minibatch
+        size -- the many-steps-per-launch kernel of small minibatches (rr_svi.hip) does not hold these children.  Any other
+        value: ValueError at ``fit``."""
 
     def __init__(self, likelihood=Gaussian(), basis=LinearBasis(), K=10, maxiter=3000, batch_size=10, updater=None,
                  nsamples=50, nstarts=500, random_state=None, sampler="host", distributed=False, gram_engine=None,
-                 devices=None, predict_engine="host"):
+                 devices=None, predict_engine="host", resident_bases="fourier"):
         self.likelihood = likelihood
         self.basis = basis
         self.K = K
@@ -151,6 +159,7 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         self.gram_engine = gram_engine  # arithmetic of the step's GEMMs (see StandardLinearModel); None = context setting
         self.devices = devices          # several GPUs behind this call, in this process (see StandardLinearModel; multigpu.py)
         self.predict_engine = predict_engine
+        self.resident_bases = resident_bases
         self.random_ = check_random_state(self.random_state)
 
     def fit(self, X, y, likelihood_args=()):
@@ -173,6 +182,8 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
     def _fit(self, X, y, likelihood_args=()):
         X, y = check_X_y(X, y)
         self._device_predictions()   # (validates predict_engine)
+        if getattr(self, "resident_bases", "fourier") not in ("fourier", "all"):
+            raise ValueError("resident_bases must be 'fourier' or 'all'")
         self._drop_serving()
         self._dev_seed = None  # the device sampler is re-keyed from random_ per fit
         N, _ = X.shape
@@ -297,8 +308,8 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
     def _resident_loop(self, params, y=None, likelihood_args=()):
         """The SGD loop with parameters, updater state and gradient in device memory (`_ResidentLoop`, rr_glm_sgd) when this
         fit is one it covers: minibatches gathered on the device; the basis a random Fourier basis, a FastFoodRBF or FastFoodGM
-        (through the dense equivalent of its chain), a LinearBasis or a concatenation of such children (Xdim <= 128, a scalar
-        regulariser each); one of
+        (through the dense equivalent of its chain), a LinearBasis -- under ``resident_bases="all"`` also a RadialBasis, SigmoidalBasis
+        or PolynomialBasis -- or a concatenation of such children (Xdim <= 128, a scalar regulariser each); one of
         the reference's likelihoods and updaters; K <= 64 (the fused small-batch loop: K <= 32); one process; one GPU, or --
         `devices=` -- every member of the device group (`_GroupResidentLoop`), or member 0 alone when the minibatches are too small
         to split.  None otherwise -- the host loop around `_elbo` then runs, with the same results."""
@@ -357,7 +368,9 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
 
     def _loop_children(self, feats, params):
         """The children of one device's MinibatchFeatures as rr_glm_sgd takes them, or None when one is not covered."""
-        from .basis_functions import _ResidentFastFood, _ResidentFastFoodGM, _ResidentLinear, _ResidentRFF
+        from .basis_functions import (_ResidentCentres, _ResidentFastFood, _ResidentFastFoodGM, _ResidentLinear, _ResidentPoly,
+                                      _ResidentRFF)
+        every = getattr(self, "resident_bases", "fourier") == "all"   # centre and polynomial children too
         kids = getattr(feats, "_kids", [])
         if not 1 <= len(kids) <= 16:
             return None
@@ -382,10 +395,14 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
                 children.append(("gm", kid.h, 2 * b.d))
             elif type(kid) is _ResidentLinear and int(np.prod(b.params.shape, dtype=int)) == 0:
                 children.append(("linear", int(kid.dX.shape[1]), bool(kid.onescol)))
+            elif every and type(kid) is _ResidentCentres and b.d <= 128 and getattr(b.params, "shape", None) in ((), (b.d,)):
+                children.append(("centres", kid.h, int(np.prod(b.params.shape, dtype=int))))
+            elif every and type(kid) is _ResidentPoly and int(np.prod(b.params.shape, dtype=int)) == 0:
+                children.append(("poly", int(kid.dX.shape[1]), bool(kid.include_bias), int(kid.order)))
             else:
                 return None
         n_par = sum(int(np.prod(getattr(p, "shape", ()), dtype=int)) for p in _flat_params(params[4]))
-        if sum(c[2] for c in children if c[0] in ("rff", "gm")) != n_par:
+        if sum(c[2] for c in children if c[0] in ("rff", "gm", "centres")) != n_par:
             return None
         return children
 
@@ -399,7 +416,7 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         # small minibatches (the reference's default is 10 rows): the whole loop inside one kernel, many steps per launch
         # (not between ranks: that kernel has no exchange step)
         if self._fused_sgd and os.environ.get("RR_GLM_FUSED", "1") != "0" and y is not None and len(likelihood_args) <= 1 \
-                and np.isfinite(self.maxiter) and comm is None and all(c[0] != "gm" for c in children):
+                and np.isfinite(self.maxiter) and comm is None and all(c[0] in ("rff", "linear") for c in children):
             N = len(y)
             M = int(min(self.batch_size, N))
             F = int(self.D_)
@@ -861,8 +878,13 @@ class _ResidentLoop(object):
         o, nk = 2 * self.glm.D_ * self.glm.K, len(self.children)
         regs = list(x[o:o + nk])
         ls, q = [], o + nk + self.n_lik
-        for c in self.children:
-            n = c[2] if c[0] in ("rff", "gm") else 0
+        feats = self.feats if hasattr(self.feats, "bases") else self.feats.feats[0]   # (a device group: member 0's)
+        for c, b in zip(self.children, feats.bases):
+            n = c[2] if c[0] in ("rff", "gm", "centres") else 0
+            if c[0] == "poly" or (c[0] == "centres" and getattr(b.params, "shape", ()) == (1,)):   # as the host loop prints them: [], (1,)
+                ls.append([] if n == 0 else x[q:q + 1])
+                q += n
+                continue
             ls.append(x[q] if n == 1 else ([x[q:q + n // 2], x[q + n // 2:q + n]] if c[0] == "gm" else x[q:q + n]))
             q += n
         return (regs[0] if nk == 1 else regs), ([x[o + nk]] if self.n_lik else []), (ls[0] if nk == 1 else ls)
