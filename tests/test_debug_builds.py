@@ -54,7 +54,22 @@ RAGGED = ["tests/test_gpu_rff.py::test_tiny_and_ragged_shapes_end_to_end", "test
           "tests/test_gpu_glm_routes.py::test_step_sequence_is_exact",
           # every instance of the FastFood chain kernels on integer data and at exactly known phases: scalar and vector
           # accesses, part waves, one to nine rows, offset pointers and leading dimensions into sentinel-filled buffers
-          "tests/test_gpu_fastfood_exact.py"]
+          "tests/test_gpu_fastfood_exact.py",
+          # every route of the Gram launchers (f32, f64, split 16-bit) bit for bit on exact data: ragged rows and widths, the
+          # rider column, prefilled accumulators, one feature matrix through shrinking and growing row counts
+          "tests/test_gpu_gram_exact.py::test_small_widths_are_exact",
+          "tests/test_gpu_gram_exact.py::test_main_kernel_routes_are_exact",
+          "tests/test_gpu_gram_exact.py::test_ragged_last_block_is_exact",
+          "tests/test_gpu_gram_exact.py::test_tile_map_routes_are_exact",
+          "tests/test_gpu_gram_exact.py::test_k_split_geometries_are_exact",
+          "tests/test_gpu_gram_exact.py::test_gram_adds_to_the_upper_triangle_only",
+          "tests/test_gpu_gram_exact.py::test_deterministic_mode_is_exact_and_repeats",
+          "tests/test_gpu_gram_exact.py::test_one_feature_matrix_through_changing_row_counts",
+          "tests/test_gpu_gram_exact.py::test_dense_gram_f32_is_exact",
+          "tests/test_gpu_gram_exact.py::test_dense_gram_f64_is_exact",
+          "tests/test_gpu_gram_exact.py::test_feature_matrix64_is_exact",
+          "tests/test_gpu_gram_exact.py::test_split_engine_three_products_are_exact",
+          "tests/test_gpu_gram_exact.py::test_split_engine_four_products_are_exact"]
 
 
 def _asan_runtime():
@@ -197,6 +212,46 @@ def test_bounds_build_counts_the_kernel_each_route_takes():
         if got != want:
             bad.append((label, got, want))
     assert len(rows) >= 30 and not bad, bad
+
+
+def _gram_variants():
+    import test_gpu_gram_exact as E
+    return [{}] + E.AB_VARIANTS
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", _gram_variants(), ids=lambda v: ",".join("%s=%s" % kv for kv in v.items()) or "default")
+def test_bounds_build_counts_the_gram_kernel_each_route_takes(variant):
+    """One Gram per case of tests/test_gpu_gram_exact.py's census under the bounds-checking build, which counts launches per
+    kernel: every SYRK, conversion, rider and gemv kernel ran as often as the module's route tables predict for this
+    device's CU count and no other one ran -- by default (the two cases of hundreds of megabytes included), and once per A/B
+    variable the launcher reads at process start.  The census shows the switch where it changes a kernel's name:
+    RR_SYRK_NO_DIAG16 (rr_syrk_f32_diag_kernel), RR_SYRK_MERGE_DIAG (rr_syrk_f32_merged_kernel), RR_SYRK_STAGGER (the flat,
+    flatstag and buf kernels) and RR_SYRK_SMALL=0 (no small kernel).  It cannot show it for RR_SYRK_DIAG_KB=64, which picks
+    rr_syrk_f32_diag16_kernel<64> -- the launch counter drops template arguments --, nor for RR_SYRK_SPLIT_SEARCH=0, which
+    changes split counts and no kernel: for those two the run holds only that the same kernels ran, and their results are
+    held by test_gpu_gram_exact.py::test_ab_variants_are_exact.  The children run one after another and share that
+    module's guard: none is started after a child, here or there, that failed, reported a bounds violation or hung."""
+    if not os.path.exists(DEBUG_LIB):
+        pytest.skip("make -C revrand_amd/csrc debug has not been run")
+    import test_gpu_gram_exact as E
+    rows = E.guarded_child("the census under %s" % (variant or "the default switches",), "print('CENSUS', json.dumps(E.census(big=%r)))\n"
+                           % (not variant), dict(variant, REVRAND_HIP_LIB=DEBUG_LIB), "CENSUS", timeout=900, forbidden=("RR_BOUNDS",))
+    bad, ran = [], set()
+    for label, cu, got, want in rows:
+        print("%-40s cu=%d %s" % (label, cu, " ".join("%s=%d" % (k.replace("rr_", "").replace("_kernel", ""), v)
+                                                      for k, v in sorted(got.items()) if v)))
+        ran |= {k for k, v in got.items() if v}
+        if got != want:
+            bad.append((label, got, want))
+    assert len(rows) >= 55 and not bad, bad
+    switched = {"RR_SYRK_NO_DIAG16": "rr_syrk_f32_diag_kernel", "RR_SYRK_MERGE_DIAG": "rr_syrk_f32_merged_kernel"}
+    switched.update({"RR_SYRK_STAGGER": ["rr_syrk_f32_flat_kernel", "rr_syrk_f32_flatstag_kernel", "rr_syrk_f32_buf_kernel"][int(v)]
+                     for k, v in variant.items() if k == "RR_SYRK_STAGGER"})
+    for k in variant:
+        assert k not in switched or switched[k] in ran, (variant, sorted(ran))
+    if variant.get("RR_SYRK_SMALL") == "0":
+        assert "rr_syrk_f32_small_kernel" not in ran
 
 
 @pytest.mark.gpu
