@@ -142,6 +142,9 @@ __global__ void __launch_bounds__(256) rr_chol_diag_kernel(double *__restrict__ 
 
 // sqrt(x) and 1 / sqrt(x) of a positive, normal x from ONE v_rsq_f64 and two coupled Newton (Goldschmidt) steps, each
 // result with a final correction (both within an ulp or two): half the dependent chain of sqrt() followed by a division.
+// At x = 4^k both results are EXACT for any seed within 2^-12: tests/test_host_logic.py::_sqrt_and_rsqrt_model repeats these
+// operations one by one (test_coupled_sqrt_and_rsqrt_is_exact_at_powers_of_four_for_any_seed), and the bit-for-bit tests of
+// tests/test_gpu_posterior_exact.py rest on it -- change the two together.
 __device__ __forceinline__ void rr_sqrt_and_rsqrt(double x, double &s, double &inv) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y, h = 0.5 * y;

@@ -69,7 +69,15 @@ RAGGED = ["tests/test_gpu_rff.py::test_tiny_and_ragged_shapes_end_to_end", "test
           "tests/test_gpu_gram_exact.py::test_dense_gram_f64_is_exact",
           "tests/test_gpu_gram_exact.py::test_feature_matrix64_is_exact",
           "tests/test_gpu_gram_exact.py::test_split_engine_three_products_are_exact",
-          "tests/test_gpu_gram_exact.py::test_split_engine_four_products_are_exact"]
+          "tests/test_gpu_gram_exact.py::test_split_engine_four_products_are_exact",
+          # every route of the device posterior bit for bit on exact dyadic data: one to ten panels and 35, ragged last panels,
+          # the cooperative kernel, refusals in every panel, the work space re-sized, the prediction factor
+          "tests/test_gpu_posterior_exact.py::test_pipeline_is_exact",
+          "tests/test_gpu_posterior_exact.py::test_scratch_follows_the_size",
+          "tests/test_gpu_posterior_exact.py::test_cooperative_kernel_is_exact",
+          "tests/test_gpu_posterior_exact.py::test_threshold_is_exact_and_a_refusal_leaves_nothing_behind",
+          "tests/test_gpu_posterior_exact.py::test_variance_factor_is_exact",
+          "tests/test_gpu_posterior_exact.py::test_variance_factor_falls_back_to_the_quadratic_form"]
 
 
 def _asan_runtime():
@@ -252,6 +260,45 @@ def test_bounds_build_counts_the_gram_kernel_each_route_takes(variant):
         assert k not in switched or switched[k] in ran, (variant, sorted(ran))
     if variant.get("RR_SYRK_SMALL") == "0":
         assert "rr_syrk_f32_small_kernel" not in ran
+
+
+def _posterior_variants():
+    import test_gpu_posterior_exact as P
+    return [{}] + P.VARIANTS
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", _posterior_variants(), ids=lambda v: ",".join("%s=%s" % kv for kv in sorted(v.items())) or "default")
+def test_bounds_build_counts_the_posterior_kernel_each_route_takes(variant):
+    """One rr_posterior_dev per size and mode of tests/test_gpu_posterior_exact.py's census (one to ten panels, the cooperative
+    kernel, the prediction factor in both forms) under the bounds-checking build, which counts launches per kernel: every
+    diagonal-block, product, SYRK, row and factor kernel ran as often as the module's restated rules predict and no other
+    one -- by default, and once per switch that rr_posterior_dev, launch_chol_diag and rr_launch_gemm_tn_f64 read at process
+    start.  Where a switch changes a kernel's name the census shows it: the two RR_CHOL_DIAG kernels ran and the default one
+    did not; with RR_GEMM64_K128=0 no K = 128 launch appears.  Where it changes only counts (pairing, look-ahead, one stream)
+    test_cases_cover_every_route asserts that the prediction differs from the default's, so `got == want` is not vacuous;
+    RR_POSDEF_EARLY_CHECK changes no launch at all and is held by its exact results alone.  Every call of the census is
+    also exact.  The children share the Gram module's guard: none is started after one that failed, reported a bounds
+    violation or hung."""
+    if not os.path.exists(DEBUG_LIB):
+        pytest.skip("make -C revrand_amd/csrc debug has not been run")
+    import test_gpu_gram_exact as E
+    import test_gpu_posterior_exact as P
+    code = P.CHILD_CODE % (sorted(variant),) + "print('CENSUS', json.dumps(P.census()))\n"
+    rows = E.guarded_child("the posterior census under %s" % P.variant_id(variant), code, dict(variant, REVRAND_HIP_LIB=DEBUG_LIB),
+                           "CENSUS", timeout=2 * P.CHILD_TIMEOUT, forbidden=("RR_BOUNDS",))
+    bad, ran = [], set()
+    for label, got, want, wrong in rows:
+        print("%-24s %s" % (label, " ".join("%s=%d" % (k.replace("rr_", "").replace("_kernel", ""), v) for k, v in sorted(got.items()) if v)))
+        ran |= {k for k, v in got.items() if v}
+        if got != want or wrong:
+            bad.append((label, got, want, wrong))
+    assert [row[0] for row in rows] == P.census_labels() and len(rows) == 25 and not bad, bad
+    chol = P.chol_kernel(variant)
+    assert chol in ran and not (set(P.CHOL_KERNELS) - {chol}) & ran, sorted(ran)
+    assert ("rr_gemm_tn_f64_k128_kernel" in ran) == (variant.get("RR_GEMM64_K128") != "0") and "rr_gemm_tn_f64_kernel" in ran
+    assert {"rr_posterior_coop_kernel", "rr_reverse_pad_kernel", "rr_ul_factor_f32_kernel", "rr_c64_to_c32_kernel",
+            "rr_syrk_f64_kernel", "rr_syrk_f64_diag_kernel", "rr_posterior_rows_kernel"} <= ran
 
 
 @pytest.mark.gpu

@@ -878,3 +878,44 @@ def test_parameter_draws_equal_scipys_without_its_overhead():
     assert _frozen_rvs(norm(), (2,), np.random.default_rng(0)) is None             # not a legacy RandomState
     p = Parameter(uniform(0.5, 1.0), Positive(), shape=(3,))
     assert np.array_equal(p.rvs(np.random.RandomState(3)), uniform(0.5, 1.0).rvs(size=(3,), random_state=np.random.RandomState(3)))
+
+
+def _sqrt_and_rsqrt_model(x, y):
+    """rr_sqrt_and_rsqrt (rr_posdef.hip) operation by operation on the seed y ~ 1 / sqrt(x), every fma rounded once.  A copy by
+    hand: the routine carries a comment that points here, and the two change together."""
+    from fractions import Fraction
+
+    def fma(a, b, c):
+        return float(Fraction(a) * Fraction(b) + Fraction(c))
+    g, h = fma(x, y, 0.0), fma(0.5, y, 0.0)
+    for _ in range(2):
+        r = fma(-h, g, 0.5)
+        g, h = fma(g, r, g), fma(h, r, h)
+    g = fma(fma(-g, g, x), h, g)
+    t = h + h
+    t = fma(t, fma(-g, t, 1.0), t)
+    return g, t
+
+
+def test_coupled_sqrt_and_rsqrt_is_exact_at_powers_of_four_for_any_seed():
+    """The diagonal-block kernels of the device posterior take sqrt and 1 / sqrt of a pivot from one v_rsq_f64 seed and coupled
+    Newton steps with a final correction each (rr_sqrt_and_rsqrt, "within an ulp or two" in general).  The exact posterior
+    tests (tests/test_gpu_posterior_exact.py) rest on more: at a pivot x = 4^k the routine must return exactly 2^k and
+    2^-k WHATEVER the hardware's seed is.  Emulated here with an exactly rounded fma for k = -17 .. 8 and every seed
+    y = 2^-k (1 + e) of a sample of |e| <= 2^-12 (far worse than the instruction's): e = 0, e = +-2^-12, e of one ulp
+    (2^-52 above, 2^-53 below 1), and 43 seeds per magnitude 2^-52, 2^-48, .., 2^-12 (the magnitude itself with both signs,
+    and random e between half of it and it)."""
+    rs = np.random.RandomState(4)
+    es = [0.0, 2.0 ** -52, -2.0 ** -53]
+    for mag in [2.0 ** -p for p in range(52, 11, -4)]:
+        es += [mag, -mag] + list(rs.choice([-1.0, 1.0], 41) * mag * rs.uniform(0.5, 1.0, 41))
+    assert 2.0 ** -12 in es and -2.0 ** -12 in es and max(abs(e) for e in es) == 2.0 ** -12
+    bad = []
+    for k in range(-17, 9):
+        x = 4.0 ** k
+        for e in es:
+            y = 2.0 ** -k * (1.0 + e)
+            s, inv = _sqrt_and_rsqrt_model(x, y)
+            if s != 2.0 ** k or inv != 2.0 ** -k:
+                bad.append((k, e, s.hex(), inv.hex()))
+    assert not bad, bad[:10]
