@@ -309,6 +309,22 @@ int rr_featmat64_pass2_rff(rr_featmat64 *fm, rr_basis *basis, const void *dX, in
                            double *dT);
 int rr_featmat64_pass2_end(rr_featmat64 *fm, double *sqErr);
 int rr_featmat64_predict_rows(rr_featmat64 *fm, double *Ey, double *Vf);
+/* RadialBasis / SigmoidalBasis and PolynomialBasis children of the float64 matrix: rr_featmat_put_centres / put_poly /
+ * pass2_centres with every product and sum in float64 (the centres and unclamped per-dimension factors of the handle's float64
+ * copies, whatever the basis' own arithmetic; device X float32 or float64 with ldx >= d, d <= 128; any col0 -- columns outside
+ * the block and the matrix' padding are left alone).  The matrix records (basis, col0, length scales) per put;
+ * rr_featmat64_pass2_centres, after rr_featmat64_pass2_rows, adds sum_{n,j} (Err m^T - Phi C)_nj dPhi_i[n,j] into dg[i]
+ * (DEVICE float64, one per length scale of that put; a (basis, col0) that was not put is refused) without dPhi, in two
+ * fixed-order stages -- no floating-point atomics, the same bits every run in either determinism mode. */
+int rr_featmat64_put_centres(rr_featmat64 *fm, rr_basis *basis, const void *dX, int x_dtype, int64_t ldx,
+                             const double *lenscale, int n_ls, int64_t col0);
+int rr_featmat64_put_poly(rr_featmat64 *fm, const void *dX, int x_dtype, int64_t ldx, int d, int order, int include_bias,
+                          int64_t col0);
+int rr_featmat64_pass2_centres(rr_featmat64 *fm, rr_basis *basis, const void *dX, int x_dtype, int64_t ldx, int64_t col0,
+                               double *dg);
+/* The rows of the current rr_featmat64_begin as they sit in HBM: out host float64 (rows, ld), ld = F rounded up to a multiple
+ * of 128, padding columns included.  For tests and diagnostics. */
+int rr_featmat64_download(rr_featmat64 *fm, double *out);
 
 /* Second data pass of _elbo / predict_moments for a concatenated basis (slm.py:160-162,193-197,240-244),
  * over the rows currently in the matrix (after rr_featmat_begin + put_*):

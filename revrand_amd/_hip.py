@@ -128,6 +128,13 @@ SIGNATURES = {
                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "rr_featmat64_pass2_end": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "rr_featmat64_predict_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rr_featmat64_put_centres": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
+    "rr_featmat64_put_poly": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "rr_featmat64_pass2_centres": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "rr_featmat64_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "rr_rff_elbo_pass2_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -1412,7 +1419,7 @@ class FeatureMatrix64(object):
     def __init__(self, max_rows, F, device=None):
         self.dev = get_device(device)
         self.lib = self.dev.lib
-        self.F, self.max_rows = int(F), int(max_rows)
+        self.F, self.max_rows, self.rows = int(F), int(max_rows), 0
         h = ctypes.c_void_p()
         _check(self.lib, self.lib.rr_featmat64_create(self.dev.ctx, self.max_rows, self.F, ctypes.byref(h)))
         self.h = h
@@ -1427,6 +1434,7 @@ class FeatureMatrix64(object):
 
     def begin(self, rows):
         _check(self.lib, self.lib.rr_featmat64_begin(self.h, rows))
+        self.rows = int(rows)
 
     def put_rff(self, handle, dX, lenscale, col0):
         ls, lsp, nls = _lenscale_arg(lenscale)
@@ -1440,6 +1448,23 @@ class FeatureMatrix64(object):
         Phi = as_float_matrix(Phi)
         _check(self.lib, self.lib.rr_featmat64_put_host(self.h, Phi.ctypes.data_as(ctypes.c_void_p), rr_dtype(Phi.dtype),
                                                         Phi.shape[1], _ld(Phi), col0))
+
+    def put_centres(self, handle, dX, lenscale, col0):
+        """RadialBasis / SigmoidalBasis features of the rows dX (float32 or float64) into columns [col0, col0 + M), in float64
+        whatever the handle's own arithmetic (rr_featmat64_put_centres)."""
+        ls, lsp, nls = _lenscale_arg(lenscale)
+        _check(self.lib, self.lib.rr_featmat64_put_centres(self.h, handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, lsp, nls, col0))
+
+    def put_poly(self, dX, order, include_bias, col0):
+        """PolynomialBasis features of the rows dX into columns [col0, col0 + include_bias + d order), powers in float64."""
+        _check(self.lib, self.lib.rr_featmat64_put_poly(self.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, dX.shape[1], int(order),
+                                                        1 if include_bias else 0, col0))
+
+    def download(self):
+        """The rows of the last `begin` as they sit in HBM, (rows, ld) float64 with the padding columns (rr_featmat64_download)."""
+        out = np.empty((self.rows, (self.F + 127) // 128 * 128), dtype=np.float64)
+        _check(self.lib, self.lib.rr_featmat64_download(self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
 
     def gram_into(self, dy, dG, db=None, dyty=None):
         _check(self.lib, self.lib.rr_featmat64_gram(self.h, _ptr(dy), rr_dtype(dy.dtype) if dy is not None else 0,
@@ -1465,6 +1490,10 @@ class FeatureMatrix64(object):
 
     def pass2_rff(self, handle, dX, col0, dT):
         _check(self.lib, self.lib.rr_featmat64_pass2_rff(self.h, handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, col0, _ptr(dT)))
+
+    def pass2_centres(self, handle, dX, col0, dg):
+        """dg += sum((Err m^T - Phi C) o dPhi_i) per length scale of a centres child, after pass2_rows, in float64."""
+        _check(self.lib, self.lib.rr_featmat64_pass2_centres(self.h, handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, col0, _ptr(dg)))
 
     def pass2_end(self):
         sq = np.zeros(1)

@@ -583,14 +583,17 @@ class _ResidentFastFoodGM(_ResidentRFF):
 class _ResidentCentres(object):
     """RadialBasis / SigmoidalBasis child: X resident as float32 (N, d); features by rr_featmat_put_centres, the length
     scales' gradient contracted on the device against the second pass' (or the GLM step's) scratch into `dg` -- one float64
-    per length scale, summed in a fixed order (rr_featmat_pass2_centres / rr_featmat_glm_centres)."""
+    per length scale, summed in a fixed order (rr_featmat_pass2_centres / rr_featmat_glm_centres).  dtype="f64": the child of a
+    float64 state (FeatureMatrix64: rr_featmat64_put_centres / rr_featmat64_pass2_centres) -- X resident as float64, every
+    product in float64 whatever the basis' own dtype; that state has no GLM step, so `gather`, `put_batch` and `glm_grad` are
+    the f32 mode's alone."""
 
     nparams = 1
 
-    def __init__(self, basis, X):
+    def __init__(self, basis, X, dtype=None):
         self.basis = basis
         self.h = basis._handle()
-        self.dX = self.h.dev.upload_matrix(np.ascontiguousarray(X, dtype=np.float32))
+        self.dX = self.h.dev.upload_matrix(np.ascontiguousarray(X, dtype=np.float64 if dtype == "f64" else np.float32))
         self.dg = self.h.dev.zeros(basis.d * 8)
 
     def put(self, fm, X, r0, rows, col0, params):
@@ -635,13 +638,14 @@ class _ResidentCentres(object):
 
 
 class _ResidentPoly(object):
-    """PolynomialBasis child: its X columns stay on the device, the powers are made there (rr_featmat_put_poly)."""
+    """PolynomialBasis child: its X columns stay on the device, the powers are made there (rr_featmat_put_poly; dtype="f64":
+    float64 columns and powers for a float64 state, rr_featmat64_put_poly)."""
 
     nparams = 0
 
-    def __init__(self, basis, X):
+    def __init__(self, basis, X, dtype=None):
         self.order, self.include_bias = basis.order, basis.include_bias
-        self.dX = _hip.get_device().upload_matrix(np.ascontiguousarray(X, dtype=np.float32))
+        self.dX = _hip.get_device().upload_matrix(np.ascontiguousarray(X, dtype=np.float64 if dtype == "f64" else np.float32))
 
     def put(self, fm, X, r0, rows, col0, params):
         fm.put_poly(_hip.DeviceView(self.dX, r0, rows), self.order, self.include_bias, col0)
@@ -1564,11 +1568,14 @@ class PolynomialBasis(Basis):
         fm.dev.sync()
         dX.free()
 
+    _f64_child = True  # `_resident_child` takes f64_children (a float64 state's opt-in, BasisCat.device_fit_state)
+
     @slice_transform
-    def _resident_child(self, X, dtype=None):
-        if dtype == "f64" or self._width(X.shape[1]) == 0:
+    def _resident_child(self, X, dtype=None, f64_children=False):
+        # a float64 state takes this child only when its maker opted in (StandardLinearModel(resident_bases="all"))
+        if (dtype == "f64" and not f64_children) or self._width(X.shape[1]) == 0:
             return None
-        return _ResidentPoly(self, X)   # (on the calling thread's device: a member's inside a device group)
+        return _ResidentPoly(self, X, dtype)   # (on the calling thread's device: a member's inside a device group)
 
     def __repr__(self):
         return "{}(order={}, include_bias={}, regularizer={})".format(type(self).__name__, self.order, self.include_bias,
@@ -1635,24 +1642,34 @@ class RadialBasis(_LengthScaleBasis):
         fm.dev.sync()
         dX.free()
 
-    def _make_child(self, X, dtype):
-        # the float64 feature matrix is not extended to these bases, nor are inputs wider than the centre tile's LDS budget
-        if dtype == "f64" or self.dtype != "f32" or X.shape[1] != self.d or self.d > 128:
+    _f64_child = True  # `_resident_child` takes f64_children (a float64 state's opt-in, BasisCat.device_fit_state)
+
+    def _make_child(self, X, dtype, f64_children=False):
+        # inputs wider than the centre tile's LDS budget have no resident child; a float64 state takes this basis -- whatever
+        # its own dtype: the float64 matrix evaluates it in float64, as it does f32 random Fourier children -- only when its
+        # maker opted in (StandardLinearModel(resident_bases="all")); an f32 state takes f32 bases
+        if X.shape[1] != self.d or self.d > 128:
+            return None
+        if dtype == "f64":
+            return _ResidentCentres(self, X, "f64") if f64_children else None
+        if self.dtype != "f32":
             return None
         return _ResidentCentres(self, X)   # (handle and rows on the calling thread's device: a member's inside a device group)
 
     @slice_transform
-    def _resident_child(self, X, dtype=None):
-        return self._make_child(X, dtype)
+    def _resident_child(self, X, dtype=None, f64_children=False):
+        return self._make_child(X, dtype, f64_children)
 
     @slice_transform
-    def device_fit_state(self, X, y):
-        """(X, y) resident for a whole fit: a one-child CatFitState (features and the length scales' gradient on the device)."""
-        child = self._make_child(X, None)
+    def device_fit_state(self, X, y, resident_bases="fourier"):
+        """(X, y) resident for a whole fit: a one-child CatFitState (features and the length scales' gradient on the device).
+        resident_bases="all": a dtype="f64" basis gets a float64 one instead of declining."""
+        dtype = "f64" if resident_bases == "all" and self.dtype == "f64" else None
+        child = self._make_child(X, dtype, f64_children=dtype == "f64")
         if child is None:
             return None
         import types
-        return CatFitState(types.SimpleNamespace(get_dim=self.get_dim, bases=[self]), [child], X, y)
+        return CatFitState(types.SimpleNamespace(get_dim=self.get_dim, bases=[self]), [child], X, y, dtype=dtype or "f32")
 
     def __repr__(self):
         return "{}(centres={}, lenscale={}, regularizer={})".format(type(self).__name__, self.C, self.params, self.regularizer)
@@ -1757,15 +1774,19 @@ class BasisCat(object):
             return G, None, None
         return G, out[F * F:F * F + F].copy(), float(out[-1])
 
-    def device_fit_state(self, X, y):
-        """(X, y) resident for a whole fit when every child can take part (random Fourier / FastFood, Linear, Bias);
-        None otherwise (the estimator then uses transform / grad)."""
+    def device_fit_state(self, X, y, resident_bases="fourier"):
+        """(X, y) resident for a whole fit when every child can take part (random Fourier / FastFood, Linear, Bias, centre and
+        polynomial bases); None otherwise (the estimator then uses transform / grad).  resident_bases="all": centre and
+        polynomial children take part in a FLOAT64 state too (by default they decline it, and with them the concatenation)."""
         # a child that asks for float64 arithmetic end to end makes the whole state float64 (rr_featmat64: float64 feature
         # matrix, f64 MFMA Gram and second pass -- the reference's arithmetic, north star's 1e-5)
         dtype = "f64" if any(getattr(b, "dtype", "f32") == "f64" for b in self.bases) else "f32"
         children = []
         for b in self.bases:
-            c = b._resident_child(X, dtype=dtype)
+            if resident_bases == "all" and getattr(b, "_f64_child", False):
+                c = b._resident_child(X, dtype=dtype, f64_children=True)
+            else:
+                c = b._resident_child(X, dtype=dtype)
             if c is None:
                 for done in children:
                     done.release()

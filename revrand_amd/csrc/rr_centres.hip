@@ -260,6 +260,175 @@ rr_poly_features_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d,
     }
 }
 
+// ---- the same three kernels in FLOAT64, for the float64 feature matrix (rr_featmat64, rr_elbo.hip) --------------------------
+// Every product and sum is float64, from Ct64 and the UNCLAMPED scale64 of centres_prepare (as the stand-alone float64
+// transform).  The centre tile is HALF the f32 kernels': CT64 = 32 centres = 16 lanes x 2 adjacent centres, so that a lane's
+// store is still 16 bytes (two doubles) and the d = 128 workgroup stays under 64 KiB of LDS (three per compute unit, as in
+// f32) instead of the 98 KB -- one workgroup per compute unit -- the f32 tile would take in doubles.
+constexpr int CT64 = 32;  // centres per tile: 16 lanes x 2 adjacent centres
+constexpr int RT64 = 16;  // rows per sub-tile: one row per thread
+
+// A workgroup owns rpb rows x CT64 columns.  Pa = P + col0 - a with a = col0 & 1, so that column 2 g of a tile is 16-byte
+// aligned whatever col0 is: lane group g holds the centres j = tile * CT64 + 2 g - a + {0, 1}; a pair that sticks out of
+// [0, M) stores its valid entry alone.  cmax = the columns of a row from Pa on (the matrix' ld - (col0 - a)).
+// LDS (doubles): the centre tile [d][CT64], the scales [d rounded up to 2], a sub-tile of RT64 rows [RT64][d + 1].
+template <typename TX, int KIND>
+__global__ void __launch_bounds__(256)
+rr_centres_features64_kernel(const TX *__restrict__ X, int64_t rows, int64_t ldx, int d, const double *__restrict__ Ct, int Mp, int M,
+                             const double *__restrict__ scale, double *__restrict__ Pa, int64_t ldp, int a, int rpb, int64_t cmax) {
+    extern __shared__ __align__(16) double smd[];
+    double *cs = smd;
+    double *ss = cs + (size_t)d * CT64;
+    double *xs = ss + ((d + 1) & ~1);
+    const int tid = threadIdx.x;
+    const int jt0 = (int)blockIdx.y * CT64 - a;  // centre behind the tile's first column
+    for (int e = tid; e < d * CT64; e += 256) {
+        const int i = e / CT64, j = jt0 + (e % CT64);
+        cs[e] = (j >= 0 && j < M) ? Ct[(size_t)i * Mp + j] : 0.0;
+    }
+    for (int i = tid; i < d; i += 256) ss[i] = scale[i];
+    const int g = tid & 15, rl = tid >> 4;
+    const int64_t rb0 = (int64_t)blockIdx.x * rpb;
+    const int64_t rb1 = rb0 + rpb < rows ? rb0 + rpb : rows;
+    const int xld = d + 1;
+    for (int64_t r0 = rb0; r0 < rb1; r0 += RT64) {
+        __syncthreads();
+        for (int e = tid; e < RT64 * d; e += 256) {
+            const int r = e / d, i = e - r * d;
+            const int64_t n = r0 + r;
+            RR_DEV_ASSERT(d <= ldx);
+            xs[r * xld + i] = n < rb1 ? (double)X[n * ldx + i] : 0.0;
+        }
+        __syncthreads();
+        double z0 = 0.0, z1 = 0.0;
+        const double *xa = xs + rl * xld;
+        for (int i = 0; i < d; ++i) {
+            const double2 c = *reinterpret_cast<const double2 *>(cs + i * CT64 + 2 * g);
+            const double s = ss[i], v = xa[i];
+            double t;
+            t = (v - c.x) * s; z0 = fma(t, t, z0);
+            t = (v - c.y) * s; z1 = fma(t, t, z1);
+        }
+        const int64_t n = r0 + rl;
+        if (n >= rb1) continue;
+        const int jb = jt0 + 2 * g;
+        const int64_t col = (int64_t)blockIdx.y * CT64 + 2 * g;
+        double2 v;
+        v.x = centres_phi<KIND, double>(z0);
+        v.y = centres_phi<KIND, double>(z1);
+        double *dst = Pa + n * ldp + col;
+        if (jb >= 0 && jb + 1 < M) {
+            RR_DEV_ASSERT(((uintptr_t)dst & 15) == 0 && col + 2 <= cmax);
+            *reinterpret_cast<double2 *>(dst) = v;
+        } else {
+            if (jb >= 0 && jb < M) {
+                RR_DEV_ASSERT(col < cmax);
+                dst[0] = v.x;
+            }
+            if (jb + 1 >= 0 && jb + 1 < M) {
+                RR_DEV_ASSERT(col + 1 < cmax);
+                dst[1] = v.y;
+            }
+        }
+    }
+}
+
+// rr_centres_contract_kernel<..., SLM = true> in float64: E = err m^T - U against the float64 matrix' P, U, err and m.  The same
+// decomposition -- w = E Phi (radial) or -E Phi (1 - Phi) (sigmoid) per entry in LDS, then per dimension sum w (x_i - c_i)^2 or
+// sum w |x_i - c_i|, times gfac_i at the end -- on tiles of RT64 rows x CT64 centres in units of (row, two centres).  Thread
+// (i, slice) as there; every product and sum is float64, added in a fixed order: per thread over its units and the block's
+// rows, across the slices in slice order, the block's nd sums to partial[block][i] (then rr_det_reduce).  No atomics.
+// LDS (all dynamic): centres [16][DP] double2, w [RT64][CT64], rows [RT64][DP + 1], the slices' sums [256].
+template <typename TX, int KIND>
+__global__ void __launch_bounds__(256)
+rr_centres_contract64_kernel(const TX *__restrict__ X, int64_t rows, int64_t ldx, int nd, int DP, const double *__restrict__ Ct, int Mp,
+                             int M, const double *__restrict__ P, const double *__restrict__ U, int64_t ldp,
+                             const double *__restrict__ err, const double *__restrict__ mvec, const GfacArgs gfac, int rpb,
+                             double *__restrict__ partial) {
+    extern __shared__ __align__(16) double smd[];
+    double2 *cs2 = reinterpret_cast<double2 *>(smd);  // [16][DP]: centres 2 q2, 2 q2 + 1 of dimension i
+    double *ws = smd + 2 * 16 * DP;                  // [RT64][CT64]
+    double *xs = ws + RT64 * CT64;                   // [RT64][DP + 1]
+    double *red = xs + RT64 * (DP + 1);              // [256]
+    const int tid = threadIdx.x;
+    const int i = tid & (DP - 1), slice = tid / DP, nsl = 256 / DP;
+    const int j0 = (int)blockIdx.y * CT64;
+    for (int e = tid; e < 16 * DP; e += 256) {
+        const int q2 = e / DP, ii = e - q2 * DP;
+        const int j = j0 + 2 * q2;
+        double2 c;
+        c.x = (ii < nd && j < M) ? Ct[(size_t)ii * Mp + j] : 0.0;
+        c.y = (ii < nd && j + 1 < M) ? Ct[(size_t)ii * Mp + j + 1] : 0.0;
+        cs2[e] = c;
+    }
+    const int64_t rb0 = (int64_t)blockIdx.x * rpb;
+    const int64_t rb1 = rb0 + rpb < rows ? rb0 + rpb : rows;
+    const int xld = DP + 1;
+    double acc = 0.0;
+    for (int64_t r0 = rb0; r0 < rb1; r0 += RT64) {
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < RT64 * CT64 / 256; ++k) {
+            const int e = tid + 256 * k, r = e >> 5, j = j0 + (e & 31);
+            const int64_t n = r0 + r;
+            double w = 0.0;
+            if (n < rb1 && j < M) {
+                RR_DEV_ASSERT(j < ldp);
+                const double phi = P[n * ldp + j], u = U[n * ldp + j];
+                const double E = fma(err[n], mvec[j], -u);
+                w = KIND == RR_CENTRES_RADIAL ? E * phi : -E * phi * (1.0 - phi);
+            }
+            ws[e] = w;
+        }
+        for (int e = tid; e < RT64 * DP; e += 256) {
+            const int r = e / DP, ii = e - r * DP;
+            const int64_t n = r0 + r;
+            RR_DEV_ASSERT(nd <= ldx);
+            xs[r * xld + ii] = (n < rb1 && ii < nd) ? (double)X[n * ldx + ii] : 0.0;
+        }
+        __syncthreads();
+        for (int u = slice; u < RT64 * 16; u += nsl) {
+            const double2 w = *reinterpret_cast<const double2 *>(ws + 2 * u), c = cs2[(u & 15) * DP + i];
+            const double x = xs[(u >> 4) * xld + i];
+            double s;
+            if (KIND == RR_CENTRES_RADIAL) {
+                const double t0 = x - c.x, t1 = x - c.y;
+                s = fma(w.x * t0, t0, w.y * t1 * t1);
+            } else {
+                s = fma(w.x, fabs(x - c.x), w.y * fabs(x - c.y));
+            }
+            acc += s;
+        }
+    }
+    red[tid] = acc;
+    __syncthreads();
+    if (tid < nd) {
+        double s = 0.0;
+        for (int sl = 0; sl < nsl; ++sl) s += red[sl * DP + tid];
+        partial[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nd + tid] = s * gfac.g[tid];
+    }
+}
+
+// rr_poly_features_kernel into the float64 matrix: the powers by repeated multiplication in float64
+template <typename TX>
+__global__ void __launch_bounds__(256)
+rr_poly_features64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, int order, int bias, double *__restrict__ P,
+                          int64_t ldp) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= N * d) return;
+    const int64_t r = t / d;
+    const int i = (int)(t - r * d);
+    RR_DEV_ASSERT(bias + (int64_t)d * order <= ldp && d <= ldx);
+    double *row = P + r * ldp;
+    if (bias && i == 0) row[0] = 1.0;
+    const double x = (double)X[r * ldx + i];
+    double p = 1.0;
+    for (int k = 0; k < order; ++k) {
+        p *= x;
+        row[bias + i * order + k] = p;
+    }
+}
+
 // ---- the resident SVI loop's side (rr_glm_sgd, rr_elbo.hip) --------------------------------------------------------
 // The d float32 feature scales of centres_prepare from the child's float64 length scales in HBM (the loop's x, after
 // rr_glm_sgd_from_log_kernel): the same clamp and isotropic broadcast, into a buffer the LOOP owns.  A zero length scale gives
@@ -645,6 +814,130 @@ int rr_featmat_pass2_centres(rr_featmat *fm, rr_basis *b, const void *dX, int x_
 
 int rr_featmat_glm_centres(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, double *dg) {
     return centres_contract<false>(fm, b, dX, x_dtype, ldx, col0, dg, "rr_featmat_glm_centres");
+}
+
+// ---- the float64 feature matrix' entry points (struct rr_featmat64: rr_internal.h) -----------------------------------------
+
+int rr_featmat64_put_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *lenscale,
+                             int n_ls, int64_t col0) {
+    CentresData *cd = centres_of(b);
+    RR_REQUIRE(fm != nullptr && cd != nullptr, "rr_featmat64_put_centres: bad argument");
+    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_featmat64_put_centres: bad dtype");
+    RR_REQUIRE(b->d <= 128, "rr_featmat64_put_centres: needs d <= 128, got %d", b->d);
+    RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "rr_featmat64_put_centres: columns out of range");
+    RR_REQUIRE(ldx >= b->d, "rr_featmat64_put_centres: device X needs ldx >= d = %d", b->d);
+    int rc = centres_prepare(b, lenscale, n_ls, "rr_featmat64_put_centres");
+    if (rc != RR_OK || fm->rows == 0) return rc;
+    RR_REQUIRE(dX != nullptr, "rr_featmat64_put_centres: null X");
+    RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
+    rc = rr_fm64_claim(fm, col0, cd->M, "rr_featmat64_put_centres");
+    if (rc != RR_OK) return rc;
+    fm->centres_puts.push_back({b, col0, std::vector<double>(lenscale, lenscale + n_ls)});  // for rr_featmat64_pass2_centres
+    const int d = b->d;
+    const int a = (int)(col0 & 1);
+    const int rpb = 256;
+    const dim3 grid((unsigned)((fm->rows + rpb - 1) / rpb), (unsigned)((a + cd->M + CT64 - 1) / CT64));
+    const size_t lds = ((size_t)d * CT64 + (size_t)((d + 1) & ~1) + (size_t)RT64 * (d + 1)) * 8;
+    double *Pa = fm->P + (col0 - a);
+    const int64_t cmax = fm->ld - (col0 - a);
+#define RR_CF64(TX, KIND)                                                                                                        \
+    hipLaunchKernelGGL((rr_centres_features64_kernel<TX, KIND>), grid, dim3(256), lds, fm->ctx->stream, (const TX *)dX, fm->rows, ldx, \
+                       d, cd->Ct64, cd->Mp, cd->M, cd->scale64, Pa, fm->ld, a, rpb, cmax)
+    if (cd->kind == RR_CENTRES_RADIAL) {
+        if (x_dtype == RR_F32) RR_CF64(float, RR_CENTRES_RADIAL);
+        else RR_CF64(double, RR_CENTRES_RADIAL);
+    } else {
+        if (x_dtype == RR_F32) RR_CF64(float, RR_CENTRES_SIGMOID);
+        else RR_CF64(double, RR_CENTRES_SIGMOID);
+    }
+#undef RR_CF64
+    RR_CHECK_HIP(hipGetLastError());
+    return RR_OK;
+}
+
+int rr_featmat64_put_poly(rr_featmat64 *fm, const void *dX, int x_dtype, int64_t ldx, int d, int order, int include_bias,
+                          int64_t col0) {
+    RR_REQUIRE(fm != nullptr && d >= 1 && ldx >= d && order >= 0, "rr_featmat64_put_poly: bad argument");
+    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_featmat64_put_poly: bad dtype");
+    const int bias = include_bias ? 1 : 0;
+    const int64_t w = bias + (int64_t)d * order;
+    RR_REQUIRE(w >= 1 && col0 >= 0 && col0 + w <= fm->F, "rr_featmat64_put_poly: columns out of range");
+    if (fm->rows == 0) return RR_OK;
+    RR_REQUIRE(dX != nullptr, "rr_featmat64_put_poly: null X");
+    RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
+    const int rc = rr_fm64_claim(fm, col0, w, "rr_featmat64_put_poly");
+    if (rc != RR_OK) return rc;
+    const dim3 grid((unsigned)((fm->rows * d + 255) / 256));
+    if (x_dtype == RR_F32)
+        hipLaunchKernelGGL(rr_poly_features64_kernel<float>, grid, dim3(256), 0, fm->ctx->stream, (const float *)dX, fm->rows, ldx, d,
+                           order, bias, fm->P + col0, fm->ld);
+    else
+        hipLaunchKernelGGL(rr_poly_features64_kernel<double>, grid, dim3(256), 0, fm->ctx->stream, (const double *)dX, fm->rows, ldx,
+                           d, order, bias, fm->P + col0, fm->ld);
+    RR_CHECK_HIP(hipGetLastError());
+    return RR_OK;
+}
+
+int rr_featmat64_pass2_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, double *dg) {
+    const char *who = "rr_featmat64_pass2_centres";
+    CentresData *cd = centres_of(b);
+    RR_REQUIRE(fm != nullptr && cd != nullptr && dg != nullptr, "%s: bad argument", who);
+    RR_REQUIRE(fm->Pt != nullptr && fm->have_rows, "%s: call rr_featmat64_pass2_rows first", who);
+    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "%s: bad dtype", who);
+    RR_REQUIRE(b->d <= 128, "%s: needs d <= 128, got %d", who, b->d);
+    RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "%s: columns out of range", who);
+    RR_REQUIRE(ldx >= b->d, "%s: device X needs ldx >= d = %d", who, b->d);
+    const std::vector<double> *put_ls = nullptr;
+    for (const auto &pc : fm->centres_puts)
+        if (pc.basis == b && pc.col0 == col0) put_ls = &pc.ls;
+    RR_REQUIRE(put_ls != nullptr, "%s: this basis was not put at column %lld since rr_featmat64_begin (rr_featmat64_put_centres)", who,
+               (long long)col0);
+    if (fm->rows == 0) return RR_OK;
+    RR_REQUIRE(dX != nullptr, "%s: null X", who);
+    const int nd = (int)put_ls->size();
+    GfacArgs gfac;
+    for (int i = 0; i < 128; ++i) {
+        const double l = i < nd ? (*put_ls)[(size_t)i] : 1.0;
+        const double g = cd->kind == RR_CENTRES_RADIAL ? 1.0 / (l * l * l) : 1.0 / (l * l);
+        gfac.g[i] = cd->kind == RR_CENTRES_RADIAL ? g * g : g;
+    }
+    rr_ctx *c = fm->ctx;
+    RR_CHECK_HIP(hipSetDevice(c->device));
+    int DP = 1;
+    while (DP < nd) DP *= 2;
+    const int ctiles = (cd->M + CT64 - 1) / CT64;
+    // about 8 workgroups per compute unit, whole sub-tiles of rows each: few enough partial sums for the second stage
+    int64_t rpb = (fm->rows * ctiles + (int64_t)c->num_cu * 8 - 1) / ((int64_t)c->num_cu * 8);
+    rpb = (rpb + RT64 - 1) / RT64 * RT64;
+    const dim3 grid((unsigned)((fm->rows + rpb - 1) / rpb), (unsigned)ctiles);
+    const int64_t nblocks = (int64_t)grid.x * grid.y;
+    void *part = nullptr;
+    int rc = rr_det_scratch(c, (size_t)nblocks * nd * 8, &part);
+    if (rc != RR_OK) return rc;
+    const size_t lds = ((size_t)2 * 16 * DP + (size_t)RT64 * CT64 + (size_t)RT64 * (DP + 1) + 256) * 8;
+    const double *P = fm->P + col0, *Uc = fm->U + col0, *mv = fm->m + col0;
+#define RR_CC64(TX, KIND)                                                                                                      \
+    hipLaunchKernelGGL((rr_centres_contract64_kernel<TX, KIND>), grid, dim3(256), lds, c->stream, (const TX *)dX, fm->rows, ldx, nd, \
+                       DP, cd->Ct64, cd->Mp, cd->M, P, Uc, fm->ld, fm->err, mv, gfac, (int)rpb, (double *)part)
+    if (cd->kind == RR_CENTRES_RADIAL) {
+        if (x_dtype == RR_F32) RR_CC64(float, RR_CENTRES_RADIAL);
+        else RR_CC64(double, RR_CENTRES_RADIAL);
+    } else {
+        if (x_dtype == RR_F32) RR_CC64(float, RR_CENTRES_SIGMOID);
+        else RR_CC64(double, RR_CENTRES_SIGMOID);
+    }
+#undef RR_CC64
+    RR_CHECK_HIP(hipGetLastError());
+    return rr_det_reduce(c, (const double *)part, nblocks, nd, nd, dg);
+}
+
+int rr_featmat64_download(rr_featmat64 *fm, double *out) {
+    RR_REQUIRE(fm != nullptr && (out != nullptr || fm->rows == 0), "rr_featmat64_download: null argument");
+    if (fm->rows == 0) return RR_OK;
+    RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
+    RR_CHECK_HIP(hipMemcpyAsync(out, fm->P, (size_t)fm->rows * fm->ld * sizeof(double), hipMemcpyDeviceToHost, fm->ctx->stream));
+    RR_CHECK_HIP(hipStreamSynchronize(fm->ctx->stream));
+    return RR_OK;
 }
 
 }  // extern "C"

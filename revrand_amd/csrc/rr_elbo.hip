@@ -4217,18 +4217,7 @@ void rr_glm_sgd_destroy(rr_glm_sgd *o) {
 // =============================================================================================
 int rr_launch_syrk_f64(rr_ctx *c, const double *P, int64_t rows, int64_t ldp, int F, double *dG, int lower_tri = 0);  // rr_rff.hip
 
-struct rr_featmat64 {
-    rr_ctx *ctx = nullptr;
-    double *P = nullptr;
-    int64_t max_rows = 0, ld = 0, rows = 0, rows_pad = 0;  // ld % 128 == 0; rows_pad = rows rounded up to 128
-    int F = 0;
-    int64_t covered = 0;
-    std::vector<std::pair<int64_t, int64_t>> spans;  // column intervals put since begin (overlaps refused)
-    // second pass / prediction scratch (allocated by the first pass2_begin)
-    double *Pt = nullptr, *U = nullptr, *Cp = nullptr, *Craw = nullptr, *m = nullptr, *dot = nullptr, *err = nullptr,
-           *sq = nullptr, *vf = nullptr;
-    bool have_rows = false;
-};
+// (struct rr_featmat64: rr_internal.h -- the centre bases' float64 entry points of rr_centres.hip share it)
 
 template <typename TX>
 __global__ void __launch_bounds__(256)
@@ -4284,7 +4273,7 @@ __global__ void __launch_bounds__(256) rr_fm64_yty_kernel(const TY *__restrict__
     if (threadIdx.x == 0) rr_acc_out(out, det, blockIdx.x, 0, part[0] + part[1] + part[2] + part[3]);
 }
 
-static int fm64_claim(rr_featmat64 *fm, int64_t col0, int64_t width, const char *who) {
+int rr_fm64_claim(rr_featmat64 *fm, int64_t col0, int64_t width, const char *who) {
     const int64_t c1 = col0 + width;
     size_t pos = 0;
     while (pos < fm->spans.size() && fm->spans[pos].first < col0) ++pos;
@@ -4376,6 +4365,7 @@ int rr_featmat64_begin(rr_featmat64 *fm, int64_t rows) {
     fm->rows_pad = (rows + 127) / 128 * 128;
     fm->covered = 0;
     fm->spans.clear();
+    fm->centres_puts.clear();
     fm->have_rows = false;
     // the children overwrite every column of [0, F) for the rows [0, rows) (checked by the consumers); the padding is ours:
     // pad rows up to the next multiple of 128 (SYRK k-blocks, GEMM tiles) and the pad columns [F, ld) of the data rows
@@ -4400,7 +4390,7 @@ int rr_featmat64_put_rff(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_dt
     if (rc != RR_OK || fm->rows == 0) return rc;
     RR_REQUIRE(dX != nullptr, "rr_featmat64_put_rff: null X");
     RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
-    rc = fm64_claim(fm, col0, 2 * (int64_t)b->n, "rr_featmat64_put_rff");
+    rc = rr_fm64_claim(fm, col0, 2 * (int64_t)b->n, "rr_featmat64_put_rff");
     if (rc != RR_OK) return rc;
     // float64 features whatever the basis' own arithmetic (its W is resident in float64 as well); whole 16-row tiles: the
     // rows up to the next multiple of 16 are written as zeros, like begin() left them
@@ -4415,7 +4405,7 @@ int rr_featmat64_put_linear(rr_featmat64 *fm, const void *dX, int x_dtype, int64
     if (fm->rows == 0) return RR_OK;
     RR_REQUIRE(dX != nullptr, "rr_featmat64_put_linear: null X");
     RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
-    int rc = fm64_claim(fm, col0, w, "rr_featmat64_put_linear");
+    int rc = rr_fm64_claim(fm, col0, w, "rr_featmat64_put_linear");
     if (rc != RR_OK) return rc;
     const dim3 grid((unsigned)((fm->rows * w + 255) / 256));
     if (x_dtype == RR_F32)
@@ -4457,7 +4447,7 @@ int rr_featmat64_put_host(rr_featmat64 *fm, const void *Phi, int dtype, int64_t 
         rr_set_error("rr_featmat64_put_host: copy failed: %s", hipGetErrorString(e));
         return RR_ERR_HIP;
     }
-    return fm64_claim(fm, col0, ncols, "rr_featmat64_put_host");
+    return rr_fm64_claim(fm, col0, ncols, "rr_featmat64_put_host");
 }
 
 int rr_featmat64_gram(rr_featmat64 *fm, const void *dy, int y_dtype, double *dG, double *db, double *dyty) {

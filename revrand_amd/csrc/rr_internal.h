@@ -233,6 +233,25 @@ struct rr_featmat {
     std::vector<CentresPut> centres_puts;
 };
 int rr_fm_claim(rr_featmat *fm, int64_t col0, int64_t width, const char *who);  // rr_featmat.hip
+
+// The float64 feature matrix of a concatenation with a dtype="f64" child (rr_elbo.hip; the centre and polynomial children's
+// entry points in rr_centres.hip).
+struct rr_featmat64 {
+    rr_ctx *ctx = nullptr;
+    double *P = nullptr;
+    int64_t max_rows = 0, ld = 0, rows = 0, rows_pad = 0;  // ld % 128 == 0; rows_pad = rows rounded up to 128
+    int F = 0;
+    int64_t covered = 0;
+    std::vector<std::pair<int64_t, int64_t>> spans;  // column intervals put since begin (overlaps refused)
+    // rr_featmat64_put_centres since rr_featmat64_begin, as rr_featmat::centres_puts: what rr_featmat64_pass2_centres contracts against
+    std::vector<rr_featmat::CentresPut> centres_puts;
+    // second pass / prediction scratch (allocated by the first pass2_begin): P^T, U = P C (ld of the matrix), C padded / as
+    // given, m (ld), P m, err (rows), sqErr, the predictive variances
+    double *Pt = nullptr, *U = nullptr, *Cp = nullptr, *Craw = nullptr, *m = nullptr, *dot = nullptr, *err = nullptr,
+           *sq = nullptr, *vf = nullptr;
+    bool have_rows = false;
+};
+int rr_fm64_claim(rr_featmat64 *fm, int64_t col0, int64_t width, const char *who);  // rr_elbo.hip
 // rr_featmat_put_rff with the length scales in device memory (rr_featmat.hip; the resident SVI loop of rr_elbo.hip)
 int rr_fm_put_rff_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *dls, int n_ls,
                       int64_t col0, const double *dshift = nullptr, double sgn = 0.0);

@@ -251,21 +251,25 @@ class ShardedFitState(object):
         self.best_on_device = False
 
     @classmethod
-    def make(cls, basis, X, y, group):
+    def make(cls, basis, X, y, group, **options):
         """None when the basis has no device-resident fit (the estimator then takes its transform / grad route on the
-        default device) or when there are fewer rows than members can share."""
+        default device) or when there are fewer rows than members can share.  options: keywords for the basis'
+        `device_fit_state` (StandardLinearModel's resident_bases), passed to every member's where it takes them."""
         make = getattr(basis, "device_fit_state", None)
         N = X.shape[0]
         if make is None or N < cls.MIN_ROWS_PER_MEMBER * group.n:
             return None
         bounds = [shard_bounds(N, i, group.n) for i in range(group.n)]
         y = np.asarray(y)
+        if options:
+            from .slm import fit_state_options
+            options = fit_state_options(make, **options)
 
         states = [None] * group.n
 
         def build(i):
             s, e = bounds[i]
-            states[i] = make(X[s:e], y[s:e])
+            states[i] = make(X[s:e], y[s:e], **options)
 
         def drop(i):
             st, states[i] = states[i], None

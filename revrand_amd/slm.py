@@ -48,6 +48,17 @@ def _scale_nested(g, s):
     return np.asarray(g, dtype=float) * s if np.ndim(g) else float(g) * s
 
 
+def fit_state_options(make, **options):
+    """The keywords of `options` that the basis' `device_fit_state` takes (the random Fourier bases' take none: their states
+    are the same under every option)."""
+    if not options:
+        return options
+    pars = _inspect.signature(make).parameters
+    if any(p.kind == p.VAR_KEYWORD for p in pars.values()):
+        return options
+    return {k: v for k, v in options.items() if k in pars}
+
+
 class StandardLinearModel(BaseEstimator, RegressorMixin):
     """Bayesian linear regression on a basis; hyper-parameters by L-BFGS-B on the ELBO.
 
@@ -70,11 +81,19 @@ class StandardLinearModel(BaseEstimator, RegressorMixin):
         Arithmetic of ``Phi^T Phi`` and ``Phi C`` for "f32" bases during ``fit`` / ``predict_moments``
         (``include/revrand_hip.h``, RR_GRAM_*): None keeps the device context's setting (exact f32 MFMA unless
         ``RR_SYRK_ENGINE`` says otherwise); "fp16x3" is ~2.5x faster at the f32 engine's accuracy.
+    resident_bases : "fourier" (default) | "all"
+        Which bases join a FLOAT64 device-resident fit (a ``dtype="f64"`` basis, or a concatenation with one).  "fourier": the
+        random Fourier and linear bases, as always -- a ``RadialBasis`` / ``SigmoidalBasis`` / ``PolynomialBasis`` makes such a
+        fit take the host route (``transform`` / ``grad``: Phi and the (N, M, d) gradient cross PCIe per evaluation).  "all":
+        those three take part as well (``rr_featmat64_put_centres`` / ``put_poly`` / ``pass2_centres``): (X, y) stay in HBM as
+        float64, neither Phi nor dPhi is formed, an f32 centre basis inside a float64 state is evaluated in float64.  f32
+        fits, ``predict_moments`` and ``distributed=True`` are the same under either value.
     """
 
     def __init__(self, basis=LinearBasis(), var=Parameter(gamma(1.), Positive()), tol=1e-8, maxiter=1000,
-                 nstarts=100, random_state=None, distributed=False, gram_engine=None, devices=None):
+                 nstarts=100, random_state=None, distributed=False, gram_engine=None, devices=None, resident_bases="fourier"):
         self.basis = basis
+        self.resident_bases = resident_bases
         self.gram_engine = gram_engine
         self.devices = devices
         self.var = var
@@ -87,6 +106,8 @@ class StandardLinearModel(BaseEstimator, RegressorMixin):
 
     def fit(self, X, y):
         """Learn (var, regularizer, basis hyper-parameters); returns self (slm.py:74-140)."""
+        if getattr(self, "resident_bases", "fourier") not in ("fourier", "all"):
+            raise ValueError("resident_bases must be 'fourier' or 'all'")
         with self._engine_scope():
             return self._fit(X, y)
 
@@ -186,12 +207,17 @@ class StandardLinearModel(BaseEstimator, RegressorMixin):
                 raise ValueError("devices= (several GPUs in this process) and distributed=True (one process per GPU) "
                                  "cannot be combined")
             from . import multigpu
-            st = multigpu.ShardedFitState.make(self.basis, X, y, group)
+            st = multigpu.ShardedFitState.make(self.basis, X, y, group, **self._state_options())
             if st is not None:
                 return st
             log.info("devices=%s: this basis / row count has no sharded device-resident fit; one GPU is used", self.devices)
         make = getattr(self.basis, "device_fit_state", None)
-        return make(X, y) if make is not None else None
+        return make(X, y, **fit_state_options(make, **self._state_options())) if make is not None else None
+
+    def _state_options(self):
+        """What `device_fit_state` is told beyond (X, y) -- nothing under the defaults, so that the call is the one it always was."""
+        every = getattr(self, "resident_bases", "fourier") == "all"
+        return {"resident_bases": "all"} if every else {}
 
     def _allreduce(self, buf):
         """Sum a float64 vector over the ranks (no-op unless distributed)."""

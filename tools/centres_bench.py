@@ -2,6 +2,7 @@
 """Kernel times of the centre bases' device kernels (docs/KERNELS.md, "Centre bases"): one JSON line.
 
     python tools/centres_bench.py [--rows 1000000] [--dim 21] [--centres 256,1024,4096] [--host-rows 20000]
+                                  [--f64-rows 20000,100000] [--f64-centres 512] [--f64-reps 3] [--f64-only]
 
 * put_centres:   rr_featmat_put_centres (RadialBasis) into a feature matrix of M columns;
 * pass2_centres: rr_featmat_pass2_centres after one rr_featmat_pass2_rows, isotropic and ARD length scales;
@@ -10,6 +11,12 @@ kernel(s) on an otherwise idle stream, launch overhead included.  With them the 
 rates: bytes written per second for the features, VALU flop per second for both.
 * host_route_s: for orientation, the wall time of the reference-style host route -- scipy's cdist + exp in float64 and
   rr_featmat_put_host of the result -- measured on --host-rows rows and scaled to --rows (cdist is linear in rows).
+* "f64": for every N of --f64-rows, one full StandardLinearModel._elbo of RadialBasis(dtype="f64") with ARD length scales
+  (--dim, --f64-centres) -- wall time, the median of --f64-reps evaluations after one warm-up evaluation -- on the host route
+  (resident_bases="fourier": transform / grad / one SYRK of [Phi | dPhi_i] per length scale) and on the float64 resident route
+  (resident_bases="all"), in this process one after the other, with their ratio; and the kernel times (events, as above) of
+  rr_featmat64_put_centres, rr_featmat64_put_poly (order 3 with bias) and rr_featmat64_pass2_centres (isotropic and ARD) at
+  that N.
 """
 import argparse
 import json
@@ -37,15 +44,102 @@ def timed(dev, fn, warm=2, reps=5):
     return float(np.median(ms))
 
 
+def elbo_seconds(SLM, basis, X, y, hyp, resident_bases, reps):
+    """Median wall time of one full `_elbo` (after one warm-up evaluation) on the route `resident_bases` gives."""
+    slm = SLM(basis, resident_bases=resident_bases)
+    slm.obj_ = -np.inf
+    slm._state = slm._make_state(X, y)
+    resident = slm._state is not None
+    try:
+        ts = []
+        for k in range(reps + 1):
+            t0 = time.perf_counter()
+            f, _ = slm._elbo(X, y, 0.5, 1.0, hyp)
+            ts.append(time.perf_counter() - t0)
+    finally:
+        if slm._state is not None:
+            slm._state.release()
+            slm._state = None
+    return float(np.median(ts[1:])), resident, float(f)
+
+
+def f64_section(a, dev):
+    from revrand_amd.slm import StandardLinearModel as SLM
+    d, M = a.dim, a.f64_centres
+    rs = np.random.RandomState(1)
+    C = rs.randn(M, d)
+    ard = np.linspace(2.0, 2.6, d)   # features of order one at d = 21
+    rows = []
+    for N in [int(v) for v in a.f64_rows.split(",") if v]:
+        X = rs.randn(N, d)
+        y = np.sin(X[:, 0] - X[:, 1]) + 0.1 * rs.randn(N)
+        row = {"N": N, "M": M, "dim": d}
+
+        def mk():
+            return RadialBasis(centres=C, lenscale=Parameter(np.ones(d), Positive()), dtype="f64")
+        resident_s, was_resident, f_res = elbo_seconds(SLM, mk(), X, y, ard, "all", a.f64_reps)
+        host_s, not_host, f_host = elbo_seconds(SLM, mk(), X, y, ard, "fourier", a.f64_reps)
+        assert was_resident and not not_host
+        row.update(elbo_host_s=host_s, elbo_resident_s=resident_s, host_over_resident=host_s / resident_s,
+                   elbo_rel_diff=abs(f_res - f_host) / abs(f_host))
+        # the three kernels on their own
+        h = mk()._handle()
+        dX, dy = dev.upload_matrix(X), dev.upload_vector(y)
+        fm = _hip.FeatureMatrix64(N, M)
+
+        def put(ls):
+            fm.begin(N)   # (clears the claimed column spans; its padding fill is outside the timed region)
+            dev.timer_start()
+            fm.put_centres(h, dX, ls, 0)
+            return dev.timer_stop()
+        for _ in range(2):
+            put(ard)
+        row["put_centres64_ms"] = float(np.median([put(ard) for _ in range(5)]))
+        row["put64_write_GBps"] = 8.0 * M * N / row["put_centres64_ms"] / 1e6
+        A = rs.randn(M, M) / np.sqrt(M)
+        fm.pass2_begin(0.1 * rs.randn(M), A @ A.T + np.eye(M))
+        dg = dev.zeros(d * 8)
+        for tag, ls in (("iso", np.array([2.3])), ("ard", ard)):
+            put(ls)
+            fm.pass2_rows(dy)
+            row["pass2_centres64_%s_ms" % tag] = timed(dev, lambda: fm.pass2_centres(h, dX, 0, dg))
+        fm.pass2_end()
+        row["pass2_64_ard_valu_Gflops"] = 4.0 * d * M * N / row["pass2_centres64_ard_ms"] / 1e6
+        del fm
+        W = 1 + 3 * d
+        fmp = _hip.FeatureMatrix64(N, W)
+
+        def put_poly():
+            fmp.begin(N)
+            dev.timer_start()
+            fmp.put_poly(dX, 3, True, 0)
+            return dev.timer_stop()
+        for _ in range(2):
+            put_poly()
+        row["put_poly64_ms"] = float(np.median([put_poly() for _ in range(5)]))
+        del fmp
+        for buf in (dX, dy, dg):
+            buf.free()
+        rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1000000)
     ap.add_argument("--dim", type=int, default=21)
     ap.add_argument("--centres", default="256,1024,4096")
     ap.add_argument("--host-rows", type=int, default=20000)
+    ap.add_argument("--f64-rows", default="20000,100000")
+    ap.add_argument("--f64-centres", type=int, default=512)
+    ap.add_argument("--f64-reps", type=int, default=3)
+    ap.add_argument("--f64-only", action="store_true")
     a = ap.parse_args()
     N, d = a.rows, a.dim
     dev = _hip.get_device()
+    if a.f64_only:
+        print(json.dumps({"dim": d, "device": dev.name, "f64": f64_section(a, dev)}))
+        return
     rs = np.random.RandomState(0)
     X = rs.randn(N, d).astype(np.float32)
     y = rs.randn(N).astype(np.float32)
@@ -96,6 +190,9 @@ def main():
         del fmh, fm
         dg.free()
         out["shapes"].append(row)
+    dX.free()
+    dy.free()
+    out["f64"] = f64_section(a, dev)
     print(json.dumps(out))
 
 
