@@ -77,7 +77,24 @@ RAGGED = ["tests/test_gpu_rff.py::test_tiny_and_ragged_shapes_end_to_end", "test
           "tests/test_gpu_posterior_exact.py::test_cooperative_kernel_is_exact",
           "tests/test_gpu_posterior_exact.py::test_threshold_is_exact_and_a_refusal_leaves_nothing_behind",
           "tests/test_gpu_posterior_exact.py::test_variance_factor_is_exact",
-          "tests/test_gpu_posterior_exact.py::test_variance_factor_falls_back_to_the_quadratic_form"]
+          "tests/test_gpu_posterior_exact.py::test_variance_factor_falls_back_to_the_quadratic_form",
+          # every route of the second pass and of predict_moments bit for bit on integer and quarter-turn data: one row to
+          # partial last row tiles, children off the tile grid, Xdim 5 .. 130, shrinking row counts, row chunks, float64
+          "tests/test_gpu_pass2_exact.py::test_quarter_turn_features_are_exact",
+          "tests/test_gpu_pass2_exact.py::test_gradient_pass_is_exact",
+          "tests/test_gpu_pass2_exact.py::test_gradient_pass_with_more_row_tiles_than_workgroups_is_exact",
+          "tests/test_gpu_pass2_exact.py::test_gradient_pass_over_the_input_dimensions_is_exact",
+          "tests/test_gpu_pass2_exact.py::test_gradient_pass_with_float64_inputs_is_exact",
+          "tests/test_gpu_pass2_exact.py::test_gradient_pass_in_deterministic_mode_is_exact_and_repeats",
+          "tests/test_gpu_pass2_exact.py::test_one_feature_matrix_through_shrinking_row_counts",
+          "tests/test_gpu_pass2_exact.py::test_gradient_pass_with_a_child_that_wrote_its_transpose",
+          "tests/test_gpu_pass2_exact.py::test_prediction_is_exact",
+          "tests/test_gpu_pass2_exact.py::test_one_feature_matrix_predicts_shrinking_row_counts",
+          "tests/test_gpu_pass2_exact.py::test_split_engines_are_exact",
+          "tests/test_gpu_pass2_exact.py::test_feature_matrix64_is_exact",
+          "tests/test_gpu_pass2_exact.py::test_basis_gradient_pass_is_exact",
+          "tests/test_gpu_pass2_exact.py::test_basis_stored_routes_are_exact",
+          "tests/test_gpu_pass2_exact.py::test_basis_prediction_is_exact"]
 
 
 def _asan_runtime():
@@ -220,6 +237,35 @@ def test_bounds_build_counts_the_kernel_each_route_takes():
         if got != want:
             bad.append((label, got, want))
     assert len(rows) >= 30 and not bad, bad
+
+
+@pytest.mark.gpu
+def test_bounds_build_counts_the_second_pass_kernel_each_route_takes():
+    """One second pass or prediction per case of tests/test_gpu_pass2_exact.py's census under the bounds-checking build,
+    which counts launches per kernel: the fused and the stored products, the pair kernel, the contraction, row and
+    feature-major kernels, the split engines' and the float32 transposes ran as often as `pass2_route`, `predict_route`
+    and `basis_route` predict for this device's CU count and no other of them ran; every counted call was exact as well.
+    The counter drops template arguments: NXB = 1 | 2 | 4 of rr_gemm_gradt_f32_kernel and DM of rr_grad_t_kernel are
+    not told apart here (that module's coverage test and exact results hold them).  The child shares the Gram module's
+    guard: it is not started after a child that failed, reported a bounds violation or hung."""
+    if not os.path.exists(DEBUG_LIB):
+        pytest.skip("make -C revrand_amd/csrc debug has not been run")
+    import test_gpu_gram_exact as E
+    import test_gpu_pass2_exact as S
+    rows = E.guarded_child("the second-pass census", S.CHILD_CODE + "print('CENSUS', json.dumps(S.census()))\n",
+                           {"REVRAND_HIP_LIB": DEBUG_LIB}, "CENSUS", timeout=900, forbidden=("RR_BOUNDS",))
+    bad, ran = [], set()
+    for label, cu, got, want, wrong in rows:
+        print("%-56s cu=%d %s" % (label, cu, " ".join("%s=%d" % (k.replace("rr_", "").replace("_kernel", ""), v)
+                                                      for k, v in sorted(got.items()) if v)))
+        ran |= {k for k, v in got.items() if v}
+        if got != want or wrong:
+            bad.append((label, {k: (got[k], want[k]) for k in got if got[k] != want[k]}, wrong))
+    assert len(rows) >= 150 and not bad, bad[:10]
+    assert {"rr_gemm_gradt_f32_kernel", "rr_gemm_tn_f32_kernel", "rr_gemm_pair_f32_kernel", "rr_grad_t_kernel", "rr_err_kernel",
+            "rr_rowdot_kernel", "rr_rowvec_kernel", "rr_transpose_f32_kernel", "rr_rff_features_t4_kernel", "rr_c64_to_c32_kernel",
+            "rr_split_bf16_kernel", "rr_syrk_b16w4_kernel", "rr_transpose_f64_kernel", "rr_rows64_kernel", "rr_err64_kernel",
+            "rr_grad_t64_kernel"} <= ran, sorted(ran)
 
 
 def _gram_variants():
