@@ -259,13 +259,16 @@ int rr_featmat_download(rr_featmat *fm, float *out);
  * streamed in row chunks); any d.  The handle is an rr_basis: rr_basis_destroy frees it. */
 #define RR_CENTRES_RADIAL 0
 #define RR_CENTRES_SIGMOID 1
+/* The widest input a centres basis may have as a DEVICE child of a feature matrix (the put / pass2 / glm entry points below,
+ * the float64 matrix' and the resident SVI loop's): above 128 columns the kernels walk the dimensions in blocks of 128. */
+#define RR_CENTRES_MAX_DIM 4096
 int rr_centres_create(rr_ctx *ctx, int kind, int compute, int d, int M, const double *C, rr_basis **out);
 int rr_centres_transform(rr_basis *basis, const void *X, int x_dtype, int64_t N, int64_t ldx, const double *lenscale,
                          int n_ls, double *Phi);
 int rr_centres_grad(rr_basis *basis, const void *X, int x_dtype, int64_t N, int64_t ldx, const double *lenscale, int n_ls,
                     double *dPhi);
 /* Phi of the rows of the current rr_featmat_begin at columns [col0, col0 + M) of a feature matrix (f32 arithmetic, device X
- * with ldx >= d, d <= 128; any col0 -- columns outside the block and the matrix' padding are left alone).  The P^T side
+ * with ldx >= d, d <= RR_CENTRES_MAX_DIM; any col0 -- columns outside the block and the matrix' padding are left alone).  The P^T side
  * copy is not written: consumers run their transposing pass.  The matrix remembers (basis, col0, length scales) for the
  * contractions below. */
 int rr_featmat_put_centres(rr_featmat *fm, rr_basis *basis, const void *dX, int x_dtype, int64_t ldx,
@@ -311,7 +314,7 @@ int rr_featmat64_pass2_end(rr_featmat64 *fm, double *sqErr);
 int rr_featmat64_predict_rows(rr_featmat64 *fm, double *Ey, double *Vf);
 /* RadialBasis / SigmoidalBasis and PolynomialBasis children of the float64 matrix: rr_featmat_put_centres / put_poly /
  * pass2_centres with every product and sum in float64 (the centres and unclamped per-dimension factors of the handle's float64
- * copies, whatever the basis' own arithmetic; device X float32 or float64 with ldx >= d, d <= 128; any col0 -- columns outside
+ * copies, whatever the basis' own arithmetic; device X float32 or float64 with ldx >= d, d <= RR_CENTRES_MAX_DIM; any col0 -- columns outside
  * the block and the matrix' padding are left alone).  The matrix records (basis, col0, length scales) per put;
  * rr_featmat64_pass2_centres, after rr_featmat64_pass2_rows, adds sum_{n,j} (Err m^T - Phi C)_nj dPhi_i[n,j] into dg[i]
  * (DEVICE float64, one per length scale of that put; a (basis, col0) that was not put is refused) without dPhi, in two
@@ -462,7 +465,8 @@ typedef struct rr_glm_sgd rr_glm_sgd;
                                  [cos | sin](VX + mX) | [cos | sin](VX - mX) (the reference's column order is cos+, sin+, cos-, sin-:  \
                                  the same blocks), n_ls = 2 Xdim coordinates [mean | length scales]                                   */
 #define RR_SGD_CHILD_CENTRES 3 /* RadialBasis / SigmoidalBasis (basis_functions.py:616-815): basis = an rr_centres_create handle with  \
-                                 f32 compute on the matrix' context, Xdim <= 128; M columns, n_ls = 1 (isotropic) or Xdim length    \
+                                 f32 compute on the matrix' context, Xdim <= RR_CENTRES_MAX_DIM (the loop's scale buffer and its   \
+                                 slots below follow Xdim / n_ls); M columns, n_ls = 1 (isotropic) or Xdim length                  \
                                  scales.  Features from the length scales in HBM, the gradient's sums in n_ls slots of the step's  \
                                  contraction buffer (all-reduced with the random Fourier children's by the group / dist steps)    */
 #define RR_SGD_CHILD_POLY 4    /* PolynomialBasis (basis_functions.py:496-576): onescol + d order columns, no parameters            */

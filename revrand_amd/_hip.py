@@ -1599,6 +1599,8 @@ class FastFoodHandle(object):
 
 
 RR_CENTRES_RADIAL, RR_CENTRES_SIGMOID = 0, 1
+CENTRES_NARROW_DIM = 128   # up to here a centre basis is a device child by default (one LDS tile holds a whole row)
+CENTRES_MAX_DIM = 4096     # RR_CENTRES_MAX_DIM (include/revrand_hip.h): the dimension-blocked kernels, behind resident_bases="all"
 
 
 class CentresHandle(object):

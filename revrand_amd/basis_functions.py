@@ -769,13 +769,17 @@ class MinibatchFeatures(object):
                 c.release()
         self.children = []
 
-    def make_resident(self, X):
+    def make_resident(self, X, resident_bases="fourier"):
         """Keep every child's columns of X on the device for a whole fit (minibatches are then gathered there by
-        index); False -- and nothing kept -- if a child cannot."""
+        index); False -- and nothing kept -- if a child cannot.  resident_bases="all" (the estimator's): centre bases of
+        129 .. 4096 input columns are children too."""
         self._drop_children()
         kids = []
         for b in self.bases:
-            c = b._resident_child(X)
+            if resident_bases == "all" and getattr(b, "_child_options", False):
+                c = b._resident_child(X, wide=True)
+            else:
+                c = b._resident_child(X)
             if c is None:
                 for k in kids:
                     k.release()
@@ -1568,11 +1572,13 @@ class PolynomialBasis(Basis):
         fm.dev.sync()
         dX.free()
 
-    _f64_child = True  # `_resident_child` takes f64_children (a float64 state's opt-in, BasisCat.device_fit_state)
+    _child_options = True  # `_resident_child` takes the options of resident_bases="all": f64_children (a float64 state's
+    #                        opt-in) and wide (inputs of more than 128 columns; the centre bases' alone, ignored otherwise)
 
     @slice_transform
-    def _resident_child(self, X, dtype=None, f64_children=False):
-        # a float64 state takes this child only when its maker opted in (StandardLinearModel(resident_bases="all"))
+    def _resident_child(self, X, dtype=None, f64_children=False, wide=False):
+        # a float64 state takes this child only when its maker opted in (StandardLinearModel(resident_bases="all")); `wide`
+        # (the centre bases' opt-in to inputs of more than 128 columns) means nothing here
         if (dtype == "f64" and not f64_children) or self._width(X.shape[1]) == 0:
             return None
         return _ResidentPoly(self, X, dtype)   # (on the calling thread's device: a member's inside a device group)
@@ -1642,13 +1648,15 @@ class RadialBasis(_LengthScaleBasis):
         fm.dev.sync()
         dX.free()
 
-    _f64_child = True  # `_resident_child` takes f64_children (a float64 state's opt-in, BasisCat.device_fit_state)
+    _child_options = True  # `_resident_child` takes the options of resident_bases="all": f64_children (a float64 state's
+    #                        opt-in) and wide (inputs of more than 128 columns; the centre bases' alone, ignored otherwise)
 
-    def _make_child(self, X, dtype, f64_children=False):
-        # inputs wider than the centre tile's LDS budget have no resident child; a float64 state takes this basis -- whatever
-        # its own dtype: the float64 matrix evaluates it in float64, as it does f32 random Fourier children -- only when its
-        # maker opted in (StandardLinearModel(resident_bases="all")); an f32 state takes f32 bases
-        if X.shape[1] != self.d or self.d > 128:
+    def _make_child(self, X, dtype, f64_children=False, wide=False):
+        # inputs wider than one LDS tile (128 columns) have a resident child -- the dimension-blocked kernels, up to
+        # RR_CENTRES_MAX_DIM columns -- only when the maker opted in (`wide`: resident_bases="all"); a float64 state takes this
+        # basis -- whatever its own dtype: the float64 matrix evaluates it in float64, as it does f32 random Fourier children --
+        # only when its maker opted in (StandardLinearModel(resident_bases="all")); an f32 state takes f32 bases
+        if X.shape[1] != self.d or self.d > (_hip.CENTRES_MAX_DIM if wide else _hip.CENTRES_NARROW_DIM):
             return None
         if dtype == "f64":
             return _ResidentCentres(self, X, "f64") if f64_children else None
@@ -1657,15 +1665,16 @@ class RadialBasis(_LengthScaleBasis):
         return _ResidentCentres(self, X)   # (handle and rows on the calling thread's device: a member's inside a device group)
 
     @slice_transform
-    def _resident_child(self, X, dtype=None, f64_children=False):
-        return self._make_child(X, dtype, f64_children)
+    def _resident_child(self, X, dtype=None, f64_children=False, wide=False):
+        return self._make_child(X, dtype, f64_children, wide=wide)
 
     @slice_transform
     def device_fit_state(self, X, y, resident_bases="fourier"):
         """(X, y) resident for a whole fit: a one-child CatFitState (features and the length scales' gradient on the device).
-        resident_bases="all": a dtype="f64" basis gets a float64 one instead of declining."""
+        resident_bases="all": a dtype="f64" basis gets a float64 one instead of declining, and inputs of 129 .. 4096 columns
+        are taken too (the dimension-blocked kernels)."""
         dtype = "f64" if resident_bases == "all" and self.dtype == "f64" else None
-        child = self._make_child(X, dtype, f64_children=dtype == "f64")
+        child = self._make_child(X, dtype, f64_children=dtype == "f64", wide=resident_bases == "all")
         if child is None:
             return None
         import types
@@ -1783,8 +1792,8 @@ class BasisCat(object):
         dtype = "f64" if any(getattr(b, "dtype", "f32") == "f64" for b in self.bases) else "f32"
         children = []
         for b in self.bases:
-            if resident_bases == "all" and getattr(b, "_f64_child", False):
-                c = b._resident_child(X, dtype=dtype, f64_children=True)
+            if resident_bases == "all" and getattr(b, "_child_options", False):
+                c = b._resident_child(X, dtype=dtype, f64_children=True, wide=True)
             else:
                 c = b._resident_child(X, dtype=dtype)
             if c is None:

@@ -38,6 +38,7 @@ struct CentresData {
 struct GfacArgs {
     double g[128];
 };
+// (a contraction over more than 128 length scales is one launch per block of 128 of them, each with its own GfacArgs)
 
 template <int KIND, typename T>
 __device__ __forceinline__ T centres_phi(T z) {
@@ -91,6 +92,87 @@ rr_centres_features_kernel(const TX *__restrict__ X, int64_t rows, int64_t ldx, 
             t = (vb - c.y) * s; z[1][1] = fmaf(t, t, z[1][1]);
             t = (vb - c.z) * s; z[1][2] = fmaf(t, t, z[1][2]);
             t = (vb - c.w) * s; z[1][3] = fmaf(t, t, z[1][3]);
+        }
+        const int jb = jt0 + 4 * g;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int64_t n = r0 + rl + 16 * h;
+            if (n >= rb1) continue;
+            float4 v;
+            v.x = centres_phi<KIND, float>(z[h][0]);
+            v.y = centres_phi<KIND, float>(z[h][1]);
+            v.z = centres_phi<KIND, float>(z[h][2]);
+            v.w = centres_phi<KIND, float>(z[h][3]);
+            float *dst = Pa + n * ldp + (int64_t)blockIdx.y * CT + 4 * g;
+            if (jb >= 0 && jb + 3 < M) {
+                RR_DEV_ASSERT(((uintptr_t)dst & 15) == 0);
+                *reinterpret_cast<float4 *>(dst) = v;
+            } else {
+                if (jb >= 0 && jb < M) dst[0] = v.x;
+                if (jb + 1 >= 0 && jb + 1 < M) dst[1] = v.y;
+                if (jb + 2 >= 0 && jb + 2 < M) dst[2] = v.z;
+                if (jb + 3 >= 0 && jb + 3 < M) dst[3] = v.w;
+            }
+        }
+    }
+}
+
+// The same for d > 128 (up to RR_CENTRES_MAX_DIM): the dimensions in blocks of DB = 128.  Per sub-tile of RT rows, block after
+// block in ascending order, the block's DB rows of the centre tile, its scales and its columns of the RT rows are reloaded into
+// the LDS layout above -- [DB][CT], [DB], [RT][DB + 1]: the budget of d = 128, 49.8 KB, three workgroups per compute unit --
+// while a lane's eight sums stay in registers.  ONE chain per (row, centre), t = (x - c) s; z = fma(t, t, z) for i = 0 .. d - 1:
+// the narrow kernel's sequence, so that no result depends on DB (a column in which x equals c adds exactly 0).  The centre
+// block is read again per sub-tile (~64 loads and a barrier against ~3 000 VALU instructions per lane and block; the load phase is
+// not overlapped with the arithmetic: 1.18x the narrow kernel's time per term at d = 256, docs/KERNELS.md 3.38).
+constexpr int DB = 128;  // dimensions per block
+
+template <typename TX, int KIND>
+__global__ void __launch_bounds__(256)
+rr_centres_features_wide_kernel(const TX *__restrict__ X, int64_t rows, int64_t ldx, int d, const float *__restrict__ Ct, int Mp, int M,
+                                const float *__restrict__ scale, float *__restrict__ Pa, int64_t ldp, int a, int rpb) {
+    extern __shared__ __align__(16) float sm[];
+    float *cs = sm;                // [DB][CT]
+    float *ss = cs + DB * CT;      // [DB]
+    float *xs = ss + DB;           // [RT][DB + 1]
+    const int tid = threadIdx.x;
+    const int jt0 = (int)blockIdx.y * CT - a;  // centre behind the tile's first column
+    const int g = tid & 15, rl = tid >> 4;
+    const int64_t rb0 = (int64_t)blockIdx.x * rpb;
+    const int64_t rb1 = rb0 + rpb < rows ? rb0 + rpb : rows;
+    constexpr int xld = DB + 1;
+    RR_DEV_ASSERT(d <= ldx);
+    for (int64_t r0 = rb0; r0 < rb1; r0 += RT) {
+        float z[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        for (int i0 = 0; i0 < d; i0 += DB) {
+            const int db = d - i0 < DB ? d - i0 : DB;
+            RR_DEV_ASSERT(db >= 1 && i0 + db <= d);
+            __syncthreads();  // the previous block's (sub-tile's) reads are over
+            for (int e = tid; e < db * CT; e += 256) {
+                const int i = e / CT, j = jt0 + (e % CT);
+                cs[e] = (j >= 0 && j < M) ? Ct[(size_t)(i0 + i) * Mp + j] : 0.f;
+            }
+            for (int i = tid; i < db; i += 256) ss[i] = scale[i0 + i];
+            for (int e = tid; e < RT * db; e += 256) {
+                const int r = e / db, i = e - r * db;
+                const int64_t n = r0 + r;
+                xs[r * xld + i] = n < rb1 ? (float)X[n * ldx + i0 + i] : 0.f;
+            }
+            __syncthreads();
+            const float *xa = xs + rl * xld, *xb = xs + (rl + 16) * xld;
+#pragma unroll 4
+            for (int i = 0; i < db; ++i) {
+                const float4 c = *reinterpret_cast<const float4 *>(cs + i * CT + 4 * g);
+                const float s = ss[i], va = xa[i], vb = xb[i];
+                float t;
+                t = (va - c.x) * s; z[0][0] = fmaf(t, t, z[0][0]);
+                t = (va - c.y) * s; z[0][1] = fmaf(t, t, z[0][1]);
+                t = (va - c.z) * s; z[0][2] = fmaf(t, t, z[0][2]);
+                t = (va - c.w) * s; z[0][3] = fmaf(t, t, z[0][3]);
+                t = (vb - c.x) * s; z[1][0] = fmaf(t, t, z[1][0]);
+                t = (vb - c.y) * s; z[1][1] = fmaf(t, t, z[1][1]);
+                t = (vb - c.z) * s; z[1][2] = fmaf(t, t, z[1][2]);
+                t = (vb - c.w) * s; z[1][3] = fmaf(t, t, z[1][3]);
+            }
         }
         const int jb = jt0 + 4 * g;
 #pragma unroll
@@ -308,6 +390,75 @@ rr_centres_features64_kernel(const TX *__restrict__ X, int64_t rows, int64_t ldx
             double t;
             t = (v - c.x) * s; z0 = fma(t, t, z0);
             t = (v - c.y) * s; z1 = fma(t, t, z1);
+        }
+        const int64_t n = r0 + rl;
+        if (n >= rb1) continue;
+        const int jb = jt0 + 2 * g;
+        const int64_t col = (int64_t)blockIdx.y * CT64 + 2 * g;
+        double2 v;
+        v.x = centres_phi<KIND, double>(z0);
+        v.y = centres_phi<KIND, double>(z1);
+        double *dst = Pa + n * ldp + col;
+        if (jb >= 0 && jb + 1 < M) {
+            RR_DEV_ASSERT(((uintptr_t)dst & 15) == 0 && col + 2 <= cmax);
+            *reinterpret_cast<double2 *>(dst) = v;
+        } else {
+            if (jb >= 0 && jb < M) {
+                RR_DEV_ASSERT(col < cmax);
+                dst[0] = v.x;
+            }
+            if (jb + 1 >= 0 && jb + 1 < M) {
+                RR_DEV_ASSERT(col + 1 < cmax);
+                dst[1] = v.y;
+            }
+        }
+    }
+}
+
+// rr_centres_features64_kernel for d > 128: the dimensions in blocks of DB, as rr_centres_features_wide_kernel -- the block's
+// centre rows [DB][CT64], scales [DB] and row sub-tile [RT64][DB + 1] in the LDS budget of d = 128 (50.3 KB), a lane's two
+// sums in registers across the blocks, one ascending fma chain per (row, centre).
+template <typename TX, int KIND>
+__global__ void __launch_bounds__(256)
+rr_centres_features64_wide_kernel(const TX *__restrict__ X, int64_t rows, int64_t ldx, int d, const double *__restrict__ Ct, int Mp, int M,
+                                  const double *__restrict__ scale, double *__restrict__ Pa, int64_t ldp, int a, int rpb, int64_t cmax) {
+    extern __shared__ __align__(16) double smd[];
+    double *cs = smd;               // [DB][CT64]
+    double *ss = cs + DB * CT64;    // [DB]
+    double *xs = ss + DB;           // [RT64][DB + 1]
+    const int tid = threadIdx.x;
+    const int jt0 = (int)blockIdx.y * CT64 - a;  // centre behind the tile's first column
+    const int g = tid & 15, rl = tid >> 4;
+    const int64_t rb0 = (int64_t)blockIdx.x * rpb;
+    const int64_t rb1 = rb0 + rpb < rows ? rb0 + rpb : rows;
+    constexpr int xld = DB + 1;
+    RR_DEV_ASSERT(d <= ldx);
+    for (int64_t r0 = rb0; r0 < rb1; r0 += RT64) {
+        double z0 = 0.0, z1 = 0.0;
+        for (int i0 = 0; i0 < d; i0 += DB) {
+            const int db = d - i0 < DB ? d - i0 : DB;
+            RR_DEV_ASSERT(db >= 1 && i0 + db <= d);
+            __syncthreads();  // the previous block's (sub-tile's) reads are over
+            for (int e = tid; e < db * CT64; e += 256) {
+                const int i = e / CT64, j = jt0 + (e % CT64);
+                cs[e] = (j >= 0 && j < M) ? Ct[(size_t)(i0 + i) * Mp + j] : 0.0;
+            }
+            for (int i = tid; i < db; i += 256) ss[i] = scale[i0 + i];
+            for (int e = tid; e < RT64 * db; e += 256) {
+                const int r = e / db, i = e - r * db;
+                const int64_t n = r0 + r;
+                xs[r * xld + i] = n < rb1 ? (double)X[n * ldx + i0 + i] : 0.0;
+            }
+            __syncthreads();
+            const double *xa = xs + rl * xld;
+#pragma unroll 4
+            for (int i = 0; i < db; ++i) {
+                const double2 c = *reinterpret_cast<const double2 *>(cs + i * CT64 + 2 * g);
+                const double s = ss[i], v = xa[i];
+                double t;
+                t = (v - c.x) * s; z0 = fma(t, t, z0);
+                t = (v - c.y) * s; z1 = fma(t, t, z1);
+            }
         }
         const int64_t n = r0 + rl;
         if (n >= rb1) continue;
@@ -555,9 +706,12 @@ int centres_host_call(rr_basis *b, const void *X, int x_dtype, int64_t N, int64_
     return rc;
 }
 
-// the contraction's launch and its second stage: dg[i] += gfac.g[i] * (the block sums in index order), i < nd
+// the contraction's launch and its second stage for the nd <= 128 length scales i0 .. i0 + nd - 1:
+// dg[i0 + i] += gfac.g[i] * (the block sums in index order), i < nd.  The per-dimension sums are independent of each other, so
+// the kernel sees columns i0 .. of X and rows i0 .. of C^T as its dimensions 0 .. nd - 1 (rr_grad_t_kernel's pattern for
+// Xdim > 128); w = E o Phi is formed again per launch.
 template <bool SLM>
-int centres_contract_launch(rr_featmat *fm, CentresData *cd, const void *dX, int x_dtype, int64_t ldx, int64_t col0, int nd,
+int centres_contract_launch(rr_featmat *fm, CentresData *cd, const void *dX, int x_dtype, int64_t ldx, int64_t col0, int i0, int nd,
                             const GfacArgs &gfac, double *dg) {
     float *U = nullptr, *err = nullptr, *m32 = nullptr;
     bool have_rows = false, have_edphi = false;
@@ -577,9 +731,10 @@ int centres_contract_launch(rr_featmat *fm, CentresData *cd, const void *dX, int
     if (rc != RR_OK) return rc;
     const size_t lds = (size_t)16 * DP * 16 + (size_t)RT * 16 * 16 + (size_t)RT * (DP + 1) * 4;
     const float *P = fm->P + col0, *Uc = U + col0, *mv = m32 + col0;
+    const float *Ct = cd->Ct32 + (size_t)i0 * cd->Mp;
 #define RR_CC(TX, KIND)                                                                                                    \
-    hipLaunchKernelGGL((rr_centres_contract_kernel<TX, KIND, SLM>), grid, dim3(256), lds, c->stream, (const TX *)dX, fm->rows, ldx, \
-                       nd, DP, cd->Ct32, cd->Mp, cd->M, P, Uc, fm->ld, err, mv, gfac, (int)rpb, (double *)part)
+    hipLaunchKernelGGL((rr_centres_contract_kernel<TX, KIND, SLM>), grid, dim3(256), lds, c->stream, (const TX *)dX + i0, fm->rows, ldx, \
+                       nd, DP, Ct, cd->Mp, cd->M, P, Uc, fm->ld, err, mv, gfac, (int)rpb, (double *)part)
     if (cd->kind == RR_CENTRES_RADIAL) {
         if (x_dtype == RR_F32) RR_CC(float, RR_CENTRES_RADIAL);
         else RR_CC(double, RR_CENTRES_RADIAL);
@@ -589,7 +744,17 @@ int centres_contract_launch(rr_featmat *fm, CentresData *cd, const void *dX, int
     }
 #undef RR_CC
     RR_CHECK_HIP(hipGetLastError());
-    return rr_det_reduce(c, (const double *)part, nblocks, nd, nd, dg);
+    return rr_det_reduce(c, (const double *)part, nblocks, nd, nd, dg + i0);
+}
+
+// gfac of the length scales ls[i0 .. i0 + 127] (n of them in all): 1 / l^6 (radial), 1 / l^2 (sigmoid); 1 behind the last
+void centres_gfac(const CentresData *cd, const std::vector<double> &ls, int i0, GfacArgs *gfac) {
+    const int n = (int)ls.size();
+    for (int i = 0; i < 128; ++i) {
+        const double l = i0 + i < n ? ls[(size_t)(i0 + i)] : 1.0;
+        const double g = cd->kind == RR_CENTRES_RADIAL ? 1.0 / (l * l * l) : 1.0 / (l * l);
+        gfac->g[i] = cd->kind == RR_CENTRES_RADIAL ? g * g : g;
+    }
 }
 
 template <bool SLM>
@@ -602,7 +767,7 @@ int centres_contract(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, i
     rr_fm_pass2_views(fm->pass2, &U, &err, &m32, &have_rows, &have_edphi);
     RR_REQUIRE(SLM ? have_rows : have_edphi, "%s: call %s first", who, SLM ? "rr_featmat_pass2_rows" : "rr_featmat_glm_step");
     RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "%s: bad dtype", who);
-    RR_REQUIRE(b->d <= 128, "%s: needs d <= 128, got %d", who, b->d);
+    RR_REQUIRE(b->d <= RR_CENTRES_MAX_DIM, "%s: needs d <= %d, got %d", who, RR_CENTRES_MAX_DIM, b->d);
     RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "%s: columns out of range", who);
     RR_REQUIRE(ldx >= b->d, "%s: device X needs ldx >= d = %d", who, b->d);
     const std::vector<double> *put_ls = nullptr;
@@ -613,13 +778,14 @@ int centres_contract(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, i
     if (fm->rows == 0) return RR_OK;
     RR_REQUIRE(dX != nullptr, "%s: null X", who);
     const int nd = (int)put_ls->size();
-    GfacArgs gfac;
-    for (int i = 0; i < 128; ++i) {
-        const double l = i < nd ? (*put_ls)[(size_t)i] : 1.0;
-        const double g = cd->kind == RR_CENTRES_RADIAL ? 1.0 / (l * l * l) : 1.0 / (l * l);
-        gfac.g[i] = cd->kind == RR_CENTRES_RADIAL ? g * g : g;
+    RR_REQUIRE(nd == 1 || nd == b->d, "%s: the block was put with %d length scales, d = %d", who, nd, b->d);
+    for (int i0 = 0; i0 < nd; i0 += 128) {  // (isotropic: dimension 0 alone, one launch)
+        GfacArgs gfac;
+        centres_gfac(cd, *put_ls, i0, &gfac);
+        const int rc = centres_contract_launch<SLM>(fm, cd, dX, x_dtype, ldx, col0, i0, nd - i0 < 128 ? nd - i0 : 128, gfac, dg);
+        if (rc != RR_OK) return rc;
     }
-    return centres_contract_launch<SLM>(fm, cd, dX, x_dtype, ldx, col0, nd, gfac, dg);
+    return RR_OK;
 }
 
 // features of fm's rows at col0 with the d float32 scales at `scale` (device), on the context's stream
@@ -628,17 +794,23 @@ void centres_launch_features(rr_featmat *fm, const CentresData *cd, int d, const
     const int a = (int)(col0 & 3);
     const int rpb = 256;
     const dim3 grid((unsigned)((fm->rows + rpb - 1) / rpb), (unsigned)((a + cd->M + CT - 1) / CT));
-    const size_t lds = ((size_t)d * CT + (size_t)((d + 3) & ~3) + (size_t)RT * (d + 1)) * 4;
+    const bool wide = d > DB;  // dimension blocks; the LDS of d = DB
+    const int dl = wide ? DB : d;
+    const size_t lds = ((size_t)dl * CT + (size_t)((dl + 3) & ~3) + (size_t)RT * (dl + 1)) * 4;
     float *Pa = fm->P + (col0 - a);
 #define RR_CF(TX, KIND)                                                                                                        \
-    hipLaunchKernelGGL((rr_centres_features_kernel<TX, KIND>), grid, dim3(256), lds, fm->ctx->stream, (const TX *)dX, fm->rows, ldx, d, \
-                       cd->Ct32, cd->Mp, cd->M, scale, Pa, fm->ld, a, rpb)
+    if (wide)                                                                                                                  \
+        hipLaunchKernelGGL((rr_centres_features_wide_kernel<TX, KIND>), grid, dim3(256), lds, fm->ctx->stream, (const TX *)dX, fm->rows, \
+                           ldx, d, cd->Ct32, cd->Mp, cd->M, scale, Pa, fm->ld, a, rpb);                                        \
+    else                                                                                                                       \
+        hipLaunchKernelGGL((rr_centres_features_kernel<TX, KIND>), grid, dim3(256), lds, fm->ctx->stream, (const TX *)dX, fm->rows, ldx, \
+                           d, cd->Ct32, cd->Mp, cd->M, scale, Pa, fm->ld, a, rpb)
     if (cd->kind == RR_CENTRES_RADIAL) {
-        if (x_dtype == RR_F32) RR_CF(float, RR_CENTRES_RADIAL);
-        else RR_CF(double, RR_CENTRES_RADIAL);
+        if (x_dtype == RR_F32) { RR_CF(float, RR_CENTRES_RADIAL); }
+        else { RR_CF(double, RR_CENTRES_RADIAL); }
     } else {
-        if (x_dtype == RR_F32) RR_CF(float, RR_CENTRES_SIGMOID);
-        else RR_CF(double, RR_CENTRES_SIGMOID);
+        if (x_dtype == RR_F32) { RR_CF(float, RR_CENTRES_SIGMOID); }
+        else { RR_CF(double, RR_CENTRES_SIGMOID); }
     }
 #undef RR_CF
 }
@@ -659,7 +831,8 @@ void rr_centres_data_free(void *p) {
 // which waits for the stream once when it has to grow -- the first step, or a larger minibatch)
 // RR_OK when b can be a RR_SGD_CHILD_CENTRES child of a loop on `ctx` with n_ls length scales; *M its width, *radial its kind
 bool rr_centres_loop_child(const rr_basis *b, const rr_ctx *ctx, int n_ls, int *M, int *radial) {
-    if (b == nullptr || b->kind != RR_KIND_CENTRES || b->centres == nullptr || b->compute != RR_F32 || b->ctx != ctx || b->d > 128 ||
+    if (b == nullptr || b->kind != RR_KIND_CENTRES || b->centres == nullptr || b->compute != RR_F32 || b->ctx != ctx ||
+        b->d > RR_CENTRES_MAX_DIM ||
         !(n_ls == 1 || n_ls == b->d))
         return false;
     const CentresData *cd = (const CentresData *)b->centres;
@@ -675,7 +848,8 @@ int rr_fm_put_centres_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dty
     CentresData *cd = centres_of(b);
     RR_REQUIRE(fm != nullptr && cd != nullptr && dls != nullptr && dscale != nullptr, "rr_fm_put_centres_dev: bad argument");
     RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_fm_put_centres_dev: bad dtype");
-    RR_REQUIRE(b->d <= 128 && (n_ls == 1 || n_ls == b->d), "rr_fm_put_centres_dev: needs d <= 128 and 1 or d length scales");
+    RR_REQUIRE(b->d <= RR_CENTRES_MAX_DIM && (n_ls == 1 || n_ls == b->d), "rr_fm_put_centres_dev: needs d <= %d and 1 or d length scales",
+               RR_CENTRES_MAX_DIM);
     RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "rr_fm_put_centres_dev: columns out of range");
     RR_REQUIRE(ldx >= b->d, "rr_fm_put_centres_dev: device X needs ldx >= d = %d", b->d);
     if (fm->rows == 0) return RR_OK;
@@ -683,7 +857,7 @@ int rr_fm_put_centres_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dty
     RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
     const int rc = rr_fm_claim(fm, col0, cd->M, "rr_fm_put_centres_dev");
     if (rc != RR_OK) return rc;
-    hipLaunchKernelGGL(rr_centres_scale_dev_kernel, dim3(1), dim3(128), 0, fm->ctx->stream, dls, n_ls, b->d,
+    hipLaunchKernelGGL(rr_centres_scale_dev_kernel, dim3((unsigned)((b->d + 127) / 128)), dim3(128), 0, fm->ctx->stream, dls, n_ls, b->d,
                        cd->kind == RR_CENTRES_RADIAL ? 1 : 0, dscale);
     centres_launch_features(fm, cd, b->d, dX, x_dtype, ldx, dscale, col0);
     RR_CHECK_HIP(hipGetLastError());
@@ -701,14 +875,19 @@ int rr_fm_glm_centres_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dty
     rr_fm_pass2_views(fm->pass2, &U, &err, &m32, &have_rows, &have_edphi);
     RR_REQUIRE(have_edphi, "rr_fm_glm_centres_dev: the step did not store EdPhi");
     RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_fm_glm_centres_dev: bad dtype");
-    RR_REQUIRE(b->d <= 128 && (n_ls == 1 || n_ls == b->d), "rr_fm_glm_centres_dev: needs d <= 128 and 1 or d length scales");
+    RR_REQUIRE(b->d <= RR_CENTRES_MAX_DIM && (n_ls == 1 || n_ls == b->d), "rr_fm_glm_centres_dev: needs d <= %d and 1 or d length scales",
+               RR_CENTRES_MAX_DIM);
     RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "rr_fm_glm_centres_dev: columns out of range");
     RR_REQUIRE(ldx >= b->d, "rr_fm_glm_centres_dev: device X needs ldx >= d = %d", b->d);
     if (fm->rows == 0) return RR_OK;
     RR_REQUIRE(dX != nullptr, "rr_fm_glm_centres_dev: null X");
     GfacArgs gfac;
     for (int i = 0; i < 128; ++i) gfac.g[i] = 1.0;
-    return centres_contract_launch<false>(fm, cd, dX, x_dtype, ldx, col0, n_ls, gfac, dS);
+    for (int i0 = 0; i0 < n_ls; i0 += 128) {
+        const int rc = centres_contract_launch<false>(fm, cd, dX, x_dtype, ldx, col0, i0, n_ls - i0 < 128 ? n_ls - i0 : 128, gfac, dS);
+        if (rc != RR_OK) return rc;
+    }
+    return RR_OK;
 }
 
 extern "C" {
@@ -769,7 +948,7 @@ int rr_featmat_put_centres(rr_featmat *fm, rr_basis *b, const void *dX, int x_dt
     CentresData *cd = centres_of(b);
     RR_REQUIRE(fm != nullptr && cd != nullptr, "rr_featmat_put_centres: bad argument");
     RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_featmat_put_centres: bad dtype");
-    RR_REQUIRE(b->d <= 128, "rr_featmat_put_centres: needs d <= 128, got %d", b->d);
+    RR_REQUIRE(b->d <= RR_CENTRES_MAX_DIM, "rr_featmat_put_centres: needs d <= %d, got %d", RR_CENTRES_MAX_DIM, b->d);
     RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "rr_featmat_put_centres: columns out of range");
     RR_REQUIRE(ldx >= b->d, "rr_featmat_put_centres: device X needs ldx >= d = %d", b->d);
     int rc = centres_prepare(b, lenscale, n_ls, "rr_featmat_put_centres");
@@ -823,7 +1002,7 @@ int rr_featmat64_put_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, int 
     CentresData *cd = centres_of(b);
     RR_REQUIRE(fm != nullptr && cd != nullptr, "rr_featmat64_put_centres: bad argument");
     RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_featmat64_put_centres: bad dtype");
-    RR_REQUIRE(b->d <= 128, "rr_featmat64_put_centres: needs d <= 128, got %d", b->d);
+    RR_REQUIRE(b->d <= RR_CENTRES_MAX_DIM, "rr_featmat64_put_centres: needs d <= %d, got %d", RR_CENTRES_MAX_DIM, b->d);
     RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "rr_featmat64_put_centres: columns out of range");
     RR_REQUIRE(ldx >= b->d, "rr_featmat64_put_centres: device X needs ldx >= d = %d", b->d);
     int rc = centres_prepare(b, lenscale, n_ls, "rr_featmat64_put_centres");
@@ -837,18 +1016,24 @@ int rr_featmat64_put_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, int 
     const int a = (int)(col0 & 1);
     const int rpb = 256;
     const dim3 grid((unsigned)((fm->rows + rpb - 1) / rpb), (unsigned)((a + cd->M + CT64 - 1) / CT64));
-    const size_t lds = ((size_t)d * CT64 + (size_t)((d + 1) & ~1) + (size_t)RT64 * (d + 1)) * 8;
+    const bool wide = d > DB;  // dimension blocks; the LDS of d = DB
+    const int dl = wide ? DB : d;
+    const size_t lds = ((size_t)dl * CT64 + (size_t)((dl + 1) & ~1) + (size_t)RT64 * (dl + 1)) * 8;
     double *Pa = fm->P + (col0 - a);
     const int64_t cmax = fm->ld - (col0 - a);
 #define RR_CF64(TX, KIND)                                                                                                        \
-    hipLaunchKernelGGL((rr_centres_features64_kernel<TX, KIND>), grid, dim3(256), lds, fm->ctx->stream, (const TX *)dX, fm->rows, ldx, \
-                       d, cd->Ct64, cd->Mp, cd->M, cd->scale64, Pa, fm->ld, a, rpb, cmax)
+    if (wide)                                                                                                                    \
+        hipLaunchKernelGGL((rr_centres_features64_wide_kernel<TX, KIND>), grid, dim3(256), lds, fm->ctx->stream, (const TX *)dX,  \
+                           fm->rows, ldx, d, cd->Ct64, cd->Mp, cd->M, cd->scale64, Pa, fm->ld, a, rpb, cmax);                     \
+    else                                                                                                                         \
+        hipLaunchKernelGGL((rr_centres_features64_kernel<TX, KIND>), grid, dim3(256), lds, fm->ctx->stream, (const TX *)dX, fm->rows, \
+                           ldx, d, cd->Ct64, cd->Mp, cd->M, cd->scale64, Pa, fm->ld, a, rpb, cmax)
     if (cd->kind == RR_CENTRES_RADIAL) {
-        if (x_dtype == RR_F32) RR_CF64(float, RR_CENTRES_RADIAL);
-        else RR_CF64(double, RR_CENTRES_RADIAL);
+        if (x_dtype == RR_F32) { RR_CF64(float, RR_CENTRES_RADIAL); }
+        else { RR_CF64(double, RR_CENTRES_RADIAL); }
     } else {
-        if (x_dtype == RR_F32) RR_CF64(float, RR_CENTRES_SIGMOID);
-        else RR_CF64(double, RR_CENTRES_SIGMOID);
+        if (x_dtype == RR_F32) { RR_CF64(float, RR_CENTRES_SIGMOID); }
+        else { RR_CF64(double, RR_CENTRES_SIGMOID); }
     }
 #undef RR_CF64
     RR_CHECK_HIP(hipGetLastError());
@@ -884,7 +1069,7 @@ int rr_featmat64_pass2_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, in
     RR_REQUIRE(fm != nullptr && cd != nullptr && dg != nullptr, "%s: bad argument", who);
     RR_REQUIRE(fm->Pt != nullptr && fm->have_rows, "%s: call rr_featmat64_pass2_rows first", who);
     RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "%s: bad dtype", who);
-    RR_REQUIRE(b->d <= 128, "%s: needs d <= 128, got %d", who, b->d);
+    RR_REQUIRE(b->d <= RR_CENTRES_MAX_DIM, "%s: needs d <= %d, got %d", who, RR_CENTRES_MAX_DIM, b->d);
     RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "%s: columns out of range", who);
     RR_REQUIRE(ldx >= b->d, "%s: device X needs ldx >= d = %d", who, b->d);
     const std::vector<double> *put_ls = nullptr;
@@ -894,41 +1079,46 @@ int rr_featmat64_pass2_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, in
                (long long)col0);
     if (fm->rows == 0) return RR_OK;
     RR_REQUIRE(dX != nullptr, "%s: null X", who);
-    const int nd = (int)put_ls->size();
-    GfacArgs gfac;
-    for (int i = 0; i < 128; ++i) {
-        const double l = i < nd ? (*put_ls)[(size_t)i] : 1.0;
-        const double g = cd->kind == RR_CENTRES_RADIAL ? 1.0 / (l * l * l) : 1.0 / (l * l);
-        gfac.g[i] = cd->kind == RR_CENTRES_RADIAL ? g * g : g;
-    }
+    const int nls = (int)put_ls->size();
+    RR_REQUIRE(nls == 1 || nls == b->d, "%s: the block was put with %d length scales, d = %d", who, nls, b->d);
     rr_ctx *c = fm->ctx;
     RR_CHECK_HIP(hipSetDevice(c->device));
-    int DP = 1;
-    while (DP < nd) DP *= 2;
     const int ctiles = (cd->M + CT64 - 1) / CT64;
     // about 8 workgroups per compute unit, whole sub-tiles of rows each: few enough partial sums for the second stage
     int64_t rpb = (fm->rows * ctiles + (int64_t)c->num_cu * 8 - 1) / ((int64_t)c->num_cu * 8);
     rpb = (rpb + RT64 - 1) / RT64 * RT64;
     const dim3 grid((unsigned)((fm->rows + rpb - 1) / rpb), (unsigned)ctiles);
     const int64_t nblocks = (int64_t)grid.x * grid.y;
-    void *part = nullptr;
-    int rc = rr_det_scratch(c, (size_t)nblocks * nd * 8, &part);
-    if (rc != RR_OK) return rc;
-    const size_t lds = ((size_t)2 * 16 * DP + (size_t)RT64 * CT64 + (size_t)RT64 * (DP + 1) + 256) * 8;
     const double *P = fm->P + col0, *Uc = fm->U + col0, *mv = fm->m + col0;
+    // one launch and one second stage per block of 128 length scales (centres_contract_launch's pattern): the kernel sees
+    // columns i0 .. of X and rows i0 .. of C^T as its dimensions 0 .. nd - 1
+    for (int i0 = 0; i0 < nls; i0 += 128) {
+        const int nd = nls - i0 < 128 ? nls - i0 : 128;
+        GfacArgs gfac;
+        centres_gfac(cd, *put_ls, i0, &gfac);
+        int DP = 1;
+        while (DP < nd) DP *= 2;
+        void *part = nullptr;
+        int rc = rr_det_scratch(c, (size_t)nblocks * nd * 8, &part);
+        if (rc != RR_OK) return rc;
+        const size_t lds = ((size_t)2 * 16 * DP + (size_t)RT64 * CT64 + (size_t)RT64 * (DP + 1) + 256) * 8;
+        const double *Ct = cd->Ct64 + (size_t)i0 * cd->Mp;
 #define RR_CC64(TX, KIND)                                                                                                      \
-    hipLaunchKernelGGL((rr_centres_contract64_kernel<TX, KIND>), grid, dim3(256), lds, c->stream, (const TX *)dX, fm->rows, ldx, nd, \
-                       DP, cd->Ct64, cd->Mp, cd->M, P, Uc, fm->ld, fm->err, mv, gfac, (int)rpb, (double *)part)
-    if (cd->kind == RR_CENTRES_RADIAL) {
-        if (x_dtype == RR_F32) RR_CC64(float, RR_CENTRES_RADIAL);
-        else RR_CC64(double, RR_CENTRES_RADIAL);
-    } else {
-        if (x_dtype == RR_F32) RR_CC64(float, RR_CENTRES_SIGMOID);
-        else RR_CC64(double, RR_CENTRES_SIGMOID);
-    }
+        hipLaunchKernelGGL((rr_centres_contract64_kernel<TX, KIND>), grid, dim3(256), lds, c->stream, (const TX *)dX + i0, fm->rows, ldx, \
+                           nd, DP, Ct, cd->Mp, cd->M, P, Uc, fm->ld, fm->err, mv, gfac, (int)rpb, (double *)part)
+        if (cd->kind == RR_CENTRES_RADIAL) {
+            if (x_dtype == RR_F32) RR_CC64(float, RR_CENTRES_RADIAL);
+            else RR_CC64(double, RR_CENTRES_RADIAL);
+        } else {
+            if (x_dtype == RR_F32) RR_CC64(float, RR_CENTRES_SIGMOID);
+            else RR_CC64(double, RR_CENTRES_SIGMOID);
+        }
 #undef RR_CC64
-    RR_CHECK_HIP(hipGetLastError());
-    return rr_det_reduce(c, (const double *)part, nblocks, nd, nd, dg);
+        RR_CHECK_HIP(hipGetLastError());
+        rc = rr_det_reduce(c, (const double *)part, nblocks, nd, nd, dg + i0);
+        if (rc != RR_OK) return rc;
+    }
+    return RR_OK;
 }
 
 int rr_featmat64_download(rr_featmat64 *fm, double *out) {

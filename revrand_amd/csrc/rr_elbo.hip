@@ -3237,8 +3237,9 @@ struct rr_glm_sgd {
     std::vector<int> col0, width, ls0;  // per child: first column, columns, first length-scale coordinate (relative to the ls block)
     std::vector<double *> dTk;          // per child (random Fourier): its (d, n) contraction inside dT; (centres): its n_ls sums S_i
     std::vector<int> radial;            // per child (centres): 1 = RadialBasis, 0 = SigmoidalBasis
-    float *cscale = nullptr;            // per child and step parity, 128 floats: a centres child's feature scales for the step's
-                                        //   length scales (rr_fm_put_centres_dev) -- the loop's own, never the handle's cache
+    float *cscale = nullptr;            // per centres child and step parity, Xdim floats at cscale0[child] + parity * Xdim: the
+    std::vector<size_t> cscale0;        //   child's feature scales for the step's length scales (rr_fm_put_centres_dev) -- the
+                                        //   loop's own, never the handle's cache
     int nkids = 0, K = 0, F = 0, n_ls = 0, n_lik = 0, updater = 0, n_h = 0;
     int64_t fk = 0, np = 0, maxiter = 0, t = 0, dT_count = 0;
     double up[4] = {0, 0, 0, 0};
@@ -3623,6 +3624,7 @@ int rr_glm_sgd_create(rr_featmat *fm, int n_children, const rr_glm_sgd_child *ch
     std::vector<SgdHRow> hrows;
     int col = 0, nls = 0;
     int64_t dT_count = 0;
+    size_t cscale_count = 0;
     for (int s = 0; s < n_children; ++s) {
         const rr_glm_sgd_child &k = children[s];
         int w = 0, is_radial = 0;
@@ -3658,8 +3660,8 @@ int rr_glm_sgd_create(rr_featmat *fm, int n_children, const rr_glm_sgd_child *ch
             int M = 0, radial = 0;
             if (!rr_centres_loop_child(k.basis, fm->ctx, k.n_ls, &M, &radial)) {
                 delete o;
-                rr_set_error("rr_glm_sgd_create: child %d must be a centres basis (rr_centres_create) with f32 compute and Xdim <= 128 on "
-                             "the matrix' context with 1 or Xdim length scales", s);
+                rr_set_error("rr_glm_sgd_create: child %d must be a centres basis (rr_centres_create) with f32 compute and Xdim <= %d on "
+                             "the matrix' context with 1 or Xdim length scales", s, RR_CENTRES_MAX_DIM);
                 return RR_ERR_INVALID;
             }
             w = M;
@@ -3689,6 +3691,8 @@ int rr_glm_sgd_create(rr_featmat *fm, int n_children, const rr_glm_sgd_child *ch
         o->width.push_back(w);
         o->ls0.push_back(nls);
         o->radial.push_back(is_radial);
+        o->cscale0.push_back(cscale_count);
+        if (k.kind == RR_SGD_CHILD_CENTRES) cscale_count += 2 * (size_t)k.basis->d;
         h_lo.push_back(col);
         h_hi.push_back(col + w);
         for (int f = col; f < col + w; ++f) h_slice[f] = s;
@@ -3730,7 +3734,7 @@ int rr_glm_sgd_create(rr_featmat *fm, int n_children, const rr_glm_sgd_child *ch
     if (e == hipSuccess) e = hipMalloc((void **)&o->h_of_ls, (size_t)(nls > 0 ? nls : 1) * sizeof(int));
     if (e == hipSuccess) e = hipMalloc((void **)&o->hrows, (size_t)(nls > 0 ? nls : 1) * sizeof(SgdHRow));
     if (e == hipSuccess) e = hipMalloc((void **)&o->ls_plain, (size_t)(nls > 0 ? nls : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&o->cscale, (size_t)n_children * 2 * 128 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&o->cscale, (cscale_count > 0 ? cscale_count : 1) * sizeof(float));
     if (e == hipSuccess) e = hipEventCreateWithFlags(&o->ev[0], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&o->ev[1], hipEventDisableTiming);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
@@ -3942,7 +3946,7 @@ static int sgd_step_front(rr_glm_sgd *o, const SgdStepIn &in) {
                 // (the scales of step t + 1 are made on THIS stream right before the kernel that reads them, in a buffer of the
                 // step's parity: step t's contraction and update on the other stream read neither)
                 rc = rr_fm_put_centres_dev(fm, k.basis, in.dX[s], in.x_dtype[s], in.ldx[s], xls + o->ls0[(size_t)s], k.n_ls,
-                                           o->cscale + ((size_t)s * 2 + (size_t)par) * 128, o->col0[(size_t)s]);
+                                           o->cscale + o->cscale0[(size_t)s] + (size_t)par * (size_t)k.basis->d, o->col0[(size_t)s]);
             } else if (k.kind == RR_SGD_CHILD_POLY)
                 rc = rr_featmat_put_poly(fm, in.dX[s], in.x_dtype[s], in.ldx[s], k.d, k.order, k.onescol, o->col0[(size_t)s]);
             else rc = rr_featmat_put_linear(fm, in.dX[s], in.x_dtype[s], in.ldx[s], k.d, k.onescol, o->col0[(size_t)s]);

@@ -137,7 +137,8 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         Which children let ``fit`` run its optimiser loop on the device (rr_glm_sgd_step and, with ``devices=`` or
         ``distributed=True`` over RCCL, its group / rank forms).  "fourier": random Fourier, FastFood and linear children, as
         before -- one RadialBasis, SigmoidalBasis or PolynomialBasis child keeps the host loop around ``_elbo``.  "all": those
-        three as well (float32 bases of Xdim <= 128 with a scalar or (d,) length scale): their features come from the length
+        three as well (float32 bases of Xdim <= 4096 with a scalar or (d,) length scale; above 128 columns the centre bases'
+        kernels walk the dimensions in blocks, and only under "all" are such bases resident at all): their features come from the length
         scales in HBM and their gradient's sums are reduced there.  Such a fit takes the step-per-call loop at every minibatch
         size -- the many-steps-per-launch kernel of small minibatches (rr_svi.hip) does not hold these children.  Any other
         value: ValueError at ``fit``."""
@@ -197,7 +198,8 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         data = (X, y) + likelihood_args
         # when every basis can keep its columns of X in HBM, minibatches are gathered there: the optimiser then
         # shuffles row INDICES (the same permutation stream) and a zero-width stand-in for X
-        self._resident_fit = self._features().make_resident(X)
+        every = getattr(self, "resident_bases", "fourier") == "all"   # (the default call is the one it always was)
+        self._resident_fit = self._features().make_resident(X, "all") if every else self._features().make_resident(X)
         if self._resident_fit:
             lazy = tuple(_LazyRows(a) if (isinstance(a, np.ndarray) and len(a) == N) else a for a in (y,) + likelihood_args)
             data = (_RowStub(N),) + lazy + (_RowIndex(N),)
@@ -309,7 +311,7 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         """The SGD loop with parameters, updater state and gradient in device memory (`_ResidentLoop`, rr_glm_sgd) when this
         fit is one it covers: minibatches gathered on the device; the basis a random Fourier basis, a FastFoodRBF or FastFoodGM
         (through the dense equivalent of its chain), a LinearBasis -- under ``resident_bases="all"`` also a RadialBasis, SigmoidalBasis
-        or PolynomialBasis -- or a concatenation of such children (Xdim <= 128, a scalar regulariser each); one of
+        or PolynomialBasis -- or a concatenation of such children (Xdim <= 128, centre bases <= 4096; a scalar regulariser each); one of
         the reference's likelihoods and updaters; K <= 64 (the fused small-batch loop: K <= 32); one process; one GPU, or --
         `devices=` -- every member of the device group (`_GroupResidentLoop`), or member 0 alone when the minibatches are too small
         to split.  None otherwise -- the host loop around `_elbo` then runs, with the same results."""
@@ -395,7 +397,8 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
                 children.append(("gm", kid.h, 2 * b.d))
             elif type(kid) is _ResidentLinear and int(np.prod(b.params.shape, dtype=int)) == 0:
                 children.append(("linear", int(kid.dX.shape[1]), bool(kid.onescol)))
-            elif every and type(kid) is _ResidentCentres and b.d <= 128 and getattr(b.params, "shape", None) in ((), (b.d,)):
+            elif every and type(kid) is _ResidentCentres and b.d <= _hip.CENTRES_MAX_DIM \
+                    and getattr(b.params, "shape", None) in ((), (b.d,)):
                 children.append(("centres", kid.h, int(np.prod(b.params.shape, dtype=int))))
             elif every and type(kid) is _ResidentPoly and int(np.prod(b.params.shape, dtype=int)) == 0:
                 children.append(("poly", int(kid.dX.shape[1]), bool(kid.include_bias), int(kid.order)))

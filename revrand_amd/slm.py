@@ -86,8 +86,10 @@ class StandardLinearModel(BaseEstimator, RegressorMixin):
         random Fourier and linear bases, as always -- a ``RadialBasis`` / ``SigmoidalBasis`` / ``PolynomialBasis`` makes such a
         fit take the host route (``transform`` / ``grad``: Phi and the (N, M, d) gradient cross PCIe per evaluation).  "all":
         those three take part as well (``rr_featmat64_put_centres`` / ``put_poly`` / ``pass2_centres``): (X, y) stay in HBM as
-        float64, neither Phi nor dPhi is formed, an f32 centre basis inside a float64 state is evaluated in float64.  f32
-        fits, ``predict_moments`` and ``distributed=True`` are the same under either value.
+        float64, neither Phi nor dPhi is formed, an f32 centre basis inside a float64 state is evaluated in float64.  "all"
+        also makes a centre basis of 129 .. 4096 input columns a device child (f32 or float64 state; the dimension-blocked
+        kernels) -- by default such a basis keeps the host route.  Other f32 fits, ``predict_moments`` and
+        ``distributed=True`` are the same under either value.
     """
 
     def __init__(self, basis=LinearBasis(), var=Parameter(gamma(1.), Positive()), tol=1e-8, maxiter=1000,

@@ -3,6 +3,7 @@
 
     python tools/centres_bench.py [--rows 1000000] [--dim 21] [--centres 256,1024,4096] [--host-rows 20000]
                                   [--f64-rows 20000,100000] [--f64-centres 512] [--f64-reps 3] [--f64-only]
+                                  [--no-host-route] [--no-f64] [--wide] [--wide-rows 3000] [--wide-reps 3]
 
 * put_centres:   rr_featmat_put_centres (RadialBasis) into a feature matrix of M columns;
 * pass2_centres: rr_featmat_pass2_centres after one rr_featmat_pass2_rows, isotropic and ARD length scales;
@@ -17,6 +18,14 @@ rates: bytes written per second for the features, VALU flop per second for both.
   (resident_bases="all"), in this process one after the other, with their ratio; and the kernel times (events, as above) of
   rr_featmat64_put_centres, rr_featmat64_put_poly (order 3 with bias) and rr_featmat64_pass2_centres (isotropic and ARD) at
   that N.
+* --dim above 128 (up to 4096) times the dimension-blocked kernels (docs/KERNELS.md 3.38); --no-host-route / --no-f64 leave
+  the host-route and "f64" parts out of such a run.
+* --wide: only the "wide" block.  "yardstick": put_centres (isotropic, M = 1024, N = 1 000 000 * 21 / d rows, so that every d
+  does the same number of (row, centre, dimension) terms) at d = 128 -- the unchanged narrow kernel -- then 256, then 128
+  again, 1024, 128 again: picoseconds per term, each d's ratio to the median d = 128 figure, and the spread (max / min - 1) of
+  the three d = 128 measurements.  "elbo": wall time of one StandardLinearModel._elbo of an ARD RadialBasis, d = 256, M = 512,
+  --wide-rows rows (3000: the default route's (N, M, d) float64 gradient is 3.1 GB), resident_bases="all" and the default
+  route evaluated alternately in one process, the median of --wide-reps each after one warm-up evaluation each.
 """
 import argparse
 import json
@@ -124,6 +133,64 @@ def f64_section(a, dev):
     return rows
 
 
+def wide_section(a, dev):
+    from revrand_amd.slm import StandardLinearModel as SLM
+    rs = np.random.RandomState(2)
+    M = 1024
+    runs = []
+    for d in (128, 256, 128, 1024, 128):
+        N = 1000000 * 21 // d
+        X = rs.randn(N, d).astype(np.float32)
+        dX = dev.upload_matrix(X)
+        h = RadialBasis(centres=rs.randn(M, d))._handle()
+        fm = _hip.FeatureMatrix(N, M)
+        ls = np.array([1.1 * d ** 0.25])
+
+        def put():
+            fm.begin(N)   # (clears the claimed column spans; its padding fill is outside the timed region)
+            dev.timer_start()
+            fm.put_centres(h, dX, ls, 0)
+            return dev.timer_stop()
+        for _ in range(2):
+            put()
+        ms = float(np.median([put() for _ in range(5)]))
+        runs.append({"dim": d, "rows": N, "M": M, "put_centres_ms": ms, "ps_per_term": ms * 1e9 / (float(N) * M * d)})
+        del fm
+        dX.free()
+    base = [r["ps_per_term"] for r in runs if r["dim"] == 128]
+    ref = float(np.median(base))
+    for r in runs:
+        r["over_d128"] = r["ps_per_term"] / ref
+    out = {"yardstick": runs, "d128_spread": max(base) / min(base) - 1.0}
+    # one _elbo on either route
+    d, M, N = 256, 512, a.wide_rows
+    X, C = rs.randn(N, d), rs.randn(M, d)
+    y = np.sin(X[:, 0] - X[:, 1]) + 0.1 * rs.randn(N)
+    hyp = 1.1 * d ** 0.25 * np.linspace(0.8, 1.3, d)
+    slms = {}
+    for rb in ("all", "fourier"):
+        slm = SLM(RadialBasis(centres=C, lenscale=Parameter(np.ones(d), Positive())), resident_bases=rb)
+        slm.obj_ = -np.inf
+        slm._state = slm._make_state(X, y)
+        assert (slm._state is not None) == (rb == "all")
+        slms[rb] = slm
+    ts, f = {"all": [], "fourier": []}, {}
+    try:
+        for k in range(a.wide_reps + 1):
+            for rb in ("all", "fourier"):   # alternately
+                t0 = time.perf_counter()
+                f[rb], _ = slms[rb]._elbo(X, y, 0.5, 1.0, hyp)
+                ts[rb].append(time.perf_counter() - t0)
+    finally:
+        slms["all"]._state.release()
+        slms["all"]._state = None
+    res, host = float(np.median(ts["all"][1:])), float(np.median(ts["fourier"][1:]))
+    out["elbo"] = {"N": N, "M": M, "dim": d, "default_tensor_GB": 8.0 * N * M * d / 1e9, "elbo_resident_s": res,
+                   "elbo_default_s": host, "default_over_resident": host / res,
+                   "elbo_rel_diff": abs(float(f["all"]) - float(f["fourier"])) / abs(float(f["fourier"]))}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1000000)
@@ -134,11 +201,19 @@ def main():
     ap.add_argument("--f64-centres", type=int, default=512)
     ap.add_argument("--f64-reps", type=int, default=3)
     ap.add_argument("--f64-only", action="store_true")
+    ap.add_argument("--no-host-route", action="store_true")
+    ap.add_argument("--no-f64", action="store_true")
+    ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--wide-rows", type=int, default=3000)
+    ap.add_argument("--wide-reps", type=int, default=3)
     a = ap.parse_args()
     N, d = a.rows, a.dim
     dev = _hip.get_device()
     if a.f64_only:
         print(json.dumps({"dim": d, "device": dev.name, "f64": f64_section(a, dev)}))
+        return
+    if a.wide:
+        print(json.dumps({"device": dev.name, "wide": wide_section(a, dev)}))
         return
     rs = np.random.RandomState(0)
     X = rs.randn(N, d).astype(np.float32)
@@ -174,25 +249,27 @@ def main():
         row["pass2_ard_read_GBps"] = 8.0 * M * N / row["pass2_centres_ard_ms"] / 1e6
         row["pass2_ard_valu_Gflops"] = 4.0 * d * M * N / row["pass2_centres_ard_ms"] / 1e6
         fm.pass2_end()
-        # the reference-style host route on a row subset
-        from scipy.spatial.distance import cdist
-        n = min(a.host_rows, N)
-        Xh = X[:n].astype(np.float64)
-        fmh = _hip.FeatureMatrix(n, M)
-        fmh.begin(n)
-        t0 = time.perf_counter()
-        den = 2 * iso ** 2
-        Phi = np.exp(-cdist(Xh / den, C / den, "sqeuclidean"))
-        fmh.put_host(Phi, 0)
-        dev.sync()
-        row["host_route_s"] = (time.perf_counter() - t0) * N / n
-        row["host_route_measured_rows"] = n
-        del fmh, fm
+        if not a.no_host_route:   # the reference-style host route on a row subset
+            from scipy.spatial.distance import cdist
+            n = min(a.host_rows, N)
+            Xh = X[:n].astype(np.float64)
+            fmh = _hip.FeatureMatrix(n, M)
+            fmh.begin(n)
+            t0 = time.perf_counter()
+            den = 2 * iso ** 2
+            Phi = np.exp(-cdist(Xh / den, C / den, "sqeuclidean"))
+            fmh.put_host(Phi, 0)
+            dev.sync()
+            row["host_route_s"] = (time.perf_counter() - t0) * N / n
+            row["host_route_measured_rows"] = n
+            del fmh
+        del fm
         dg.free()
         out["shapes"].append(row)
     dX.free()
     dy.free()
-    out["f64"] = f64_section(a, dev)
+    if not a.no_f64:
+        out["f64"] = f64_section(a, dev)
     print(json.dumps(out))
 
 
