@@ -519,8 +519,17 @@ void rr_glm_sgd_destroy(rr_glm_sgd *s);
  * updater, -ELBO and |gradient| per step -- float64 throughout (draws are float32 values).  Same children, z layout, updaters
  * and likelihoods as rr_glm_sgd; rr_glm_svi_supported says whether a shape is in range (F K and minibatch x F small enough for
  * one CU's LDS).
- * RR_SGD_CHILD_CENTRES and RR_SGD_CHILD_POLY children are NOT taken (rr_glm_svi_create: RR_ERR_INVALID): those fits run
- * rr_glm_sgd_step at every minibatch size.
+ * rr_glm_svi_create takes RR_SGD_CHILD_RFF and RR_SGD_CHILD_LINEAR children and refuses RR_SGD_CHILD_CENTRES and
+ * RR_SGD_CHILD_POLY (RR_ERR_INVALID), as it always did.  rr_glm_svi_create_all -- same arguments, same object -- takes those two
+ * as well: a centres child's features and its length scales' gradient (n_ls slots next to the random Fourier children's) and a
+ * polynomial child's powers are formed inside the kernel in float64, from the handle's float64 copy of the centres held in LDS
+ * for the whole launch.  The handle is an rr_centres_create handle of `ctx` with n_ls = 1 or Xdim; its compute dtype does not
+ * matter here (RR_F32 and RR_F64 handles alike: this kernel is float64 whatever the handle computes in elsewhere).  A polynomial
+ * child needs d >= 1, order >= 0 and at least one column (order >= 1 or include_bias).  RR_SGD_CHILD_GM is refused by both.
+ * rr_glm_svi_supported_all is the range check of rr_glm_svi_create_all: table_entries = the exact number of doubles of all
+ * tables held in LDS, sum over the random Fourier children of Xdim x n plus sum over the centre children of Xdim x centres
+ * (rr_glm_svi_supported bounds it by dsum (F / 2 + 1), which holds for random Fourier children only).  The minibatch's rows
+ * are held in registers between their loads and their use: minibatch x dsum <= 1024 bounds the input width.
  * dX[c], x_dtype[c], ldx[c]: child c's RESIDENT rows of its columns of X (all N rows, device); dy / drowarg: targets and the
  * binomial's n for all N rows (device, dtype); dlconst: per row, the part of loglike that does not depend on f (device float64:
  * Poisson -lgamma(y + 1), binomial lgamma(n + 1) - lgamma(y + 1) - lgamma(n - y + 1); NULL: zero -- Bernoulli, Gaussian);
@@ -532,6 +541,12 @@ int rr_glm_svi_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *child
                       int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
                       const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
                       rr_glm_svi **out);
+int rr_glm_svi_supported_all(int F, int K, int L, int M, int n_children, int dsum, int n_ls, int table_entries);
+int rr_glm_svi_create_all(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                          const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype,
+                          int K, int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
+                          const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
+                          rr_glm_svi **out);
 /* The start point (structured_sgd picks it after the random starts, decorators.py:223-234), the bounds and the log-space
  * flags as logtrick_sgd leaves them (decorators.py:586-616), before the first step; NULL: unchanged. */
 int rr_glm_svi_set_start(rr_glm_svi *s, const double *z0, const double *lower, const double *upper, const unsigned char *is_log);

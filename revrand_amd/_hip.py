@@ -196,6 +196,12 @@ SIGNATURES = {
                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                          ctypes.c_int64, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]),
+    "rr_glm_svi_supported_all": (ctypes.c_int, [ctypes.c_int] * 8),
+    "rr_glm_svi_create_all": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]),
     "rr_glm_svi_set_start": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rr_glm_svi_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                       ctypes.c_uint64]),
@@ -1328,10 +1334,12 @@ class FusedSvi(object):
     """The SVI loop for small minibatches, many steps per launch (rr_glm_svi, rr_svi.hip).
     children: ("rff", RffHandle, n_ls, dX) | ("linear", d, onescol, dX) in concatenation order, dX the child's RESIDENT
     rows (DeviceMatrix, all N rows); dy / drowarg: DeviceBuffers of all N targets / per-row arguments.  ResidentSgd's "centres"
-    and "poly" tuples (+ dX) are passed on as they are and refused by the library: that kernel does not hold them."""
+    and "poly" tuples (+ dX) are passed on as they are: refused by the library's rr_glm_svi_create (the default), taken by
+    rr_glm_svi_create_all (all_children=True), which forms their features and the length scales' gradient inside the kernel in
+    float64 (a "gm" child is refused by both)."""
 
     def __init__(self, dev, children, N, dy, drowarg, dlconst, K, L, M, lik, n_lik, z0, lower, upper, is_log, updater_id, updater_par,
-                 maxiter, bmag):
+                 maxiter, bmag, all_children=False):
         self.dev, self.lib, self.children = dev, dev.lib, list(children)
         self._keep = (dy, drowarg, dlconst)
         z0 = np.ascontiguousarray(z0, dtype=np.float64)
@@ -1346,7 +1354,7 @@ class FusedSvi(object):
             dX = ch[-1]
             n_ls += _fill_sgd_child(k, ch[:-1])
             F += {"rff": lambda: 2 * ch[1].n, "gm": lambda: 4 * ch[1].n, "centres": lambda: ch[1].M,
-                  "poly": lambda: (1 if ch[2] else 0) + int(ch[1]) * int(ch[3]),
+                  "poly": lambda: (1 if ch[2] else 0) + int(ch[1]) * max(int(ch[3]), 0),   # (a negative order: the library's to refuse)
                   "linear": lambda: int(ch[1]) + (1 if ch[2] else 0)}[ch[0]]()
             p = dX.ptr
             ptrs[i] = p if isinstance(p, int) else p.value
@@ -1359,7 +1367,8 @@ class FusedSvi(object):
         par[:len(updater_par)] = updater_par
         self.maxiter = int(maxiter)
         h = ctypes.c_void_p()
-        _check(self.lib, self.lib.rr_glm_svi_create(
+        create = self.lib.rr_glm_svi_create_all if all_children else self.lib.rr_glm_svi_create
+        _check(self.lib, create(
             dev.ctx, nk, ctypes.cast(kids, ctypes.c_void_p), ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(dts, ctypes.c_void_p),
             ctypes.cast(lds, ctypes.c_void_p), int(N), _ptr(dy), _ptr(drowarg), _ptr(dlconst), rr_dtype(dy.dtype), self.K, self.L, self.M,
             int(lik), int(n_lik), z0.ctypes.data_as(ctypes.c_void_p), lower.ctypes.data_as(ctypes.c_void_p),
@@ -1408,6 +1417,13 @@ class FusedSvi(object):
 
 def svi_supported(F, K, L, M, n_children, dsum, n_ls):
     return bool(load_library().rr_glm_svi_supported(int(F), int(K), int(L), int(M), int(n_children), int(dsum), int(n_ls)))
+
+
+def svi_supported_all(F, K, L, M, n_children, dsum, n_ls, table_entries):
+    """rr_glm_svi_supported_all: the range of FusedSvi(..., all_children=True); table_entries = the doubles of every random
+    Fourier child's W (Xdim x n) and every centre child's table (Xdim x centres) together."""
+    return bool(load_library().rr_glm_svi_supported_all(int(F), int(K), int(L), int(M), int(n_children), int(dsum), int(n_ls),
+                                                        int(min(table_entries, 2 ** 31 - 1))))
 
 
 class FeatureMatrix64(object):

@@ -841,6 +841,19 @@ bool rr_centres_loop_child(const rr_basis *b, const rr_ctx *ctx, int n_ls, int *
     return true;
 }
 
+// What the fused small-minibatch loop (rr_svi.hip) takes of a centres handle: it computes in float64 from the handle's float64
+// copy of C^T (row length *Mp), whatever the handle's own compute dtype, and needs no dimension blocking (its own limits bound d)
+bool rr_centres_svi_child(const rr_basis *b, const rr_ctx *ctx, int n_ls, int *M, int *Mp, int *radial, const double **Ct64) {
+    if (b == nullptr || b->kind != RR_KIND_CENTRES || b->centres == nullptr || b->ctx != ctx || !(n_ls == 1 || n_ls == b->d)) return false;
+    const CentresData *cd = (const CentresData *)b->centres;
+    if (cd->Ct64 == nullptr) return false;
+    *M = cd->M;
+    *Mp = cd->Mp;
+    *radial = cd->kind == RR_CENTRES_RADIAL ? 1 : 0;
+    *Ct64 = cd->Ct64;
+    return true;
+}
+
 // rr_featmat_put_centres with the n_ls float64 length scales at dls (device): their float32 scales go to dscale (d floats
 // the CALLER owns -- neither the handle's cache nor a centres_puts record is touched), then the feature kernel reads them
 int rr_fm_put_centres_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *dls, int n_ls,

@@ -258,6 +258,7 @@ int rr_fm_put_rff_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, 
 // RadialBasis / SigmoidalBasis children of the resident SVI loop (rr_centres.hip): whether b can be one; its features from
 // length scales in device memory through a scale buffer the caller owns; the raw sums S_i of its length scales' gradient
 bool rr_centres_loop_child(const rr_basis *b, const rr_ctx *ctx, int n_ls, int *M, int *radial);
+bool rr_centres_svi_child(const rr_basis *b, const rr_ctx *ctx, int n_ls, int *M, int *Mp, int *radial, const double **Ct64);
 int rr_fm_put_centres_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *dls, int n_ls,
                           float *dscale, int64_t col0);
 int rr_fm_glm_centres_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, int n_ls, double *dS);

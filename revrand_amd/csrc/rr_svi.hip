@@ -28,6 +28,10 @@
 // so a step costs two device-scope barriers (one of them split-phase) instead of thirty launches.  Everything is float64
 // (the draws are float32 values, as everywhere on this path).  The K workgroups must be co-resident (K <= 32 of 256 CUs).
 //
+// Children: random Fourier and linear (rr_glm_svi_create); rr_glm_svi_create_all also takes RadialBasis / SigmoidalBasis
+// (RR_SGD_CHILD_CENTRES: the centres in LDS next to the W tables, features and the length scales' sums in phases c and f,
+// the factor 1 / l^6 or 1 / l^2 once in phase i) and PolynomialBasis (RR_SGD_CHILD_POLY: powers in phase c, no parameters).
+//
 // rr_glm_svi_starts evaluates the random starts of structured_sgd (decorators.py:541-583) -- nstarts candidates, each on its
 // own minibatch with its own draws -- as ONE launch, one workgroup per candidate (objective only).
 #include "rr_internal.h"
@@ -43,10 +47,17 @@ namespace {
 
 struct SviChild {
     int kind, col0, width, d, n, n_ls, ls0, onescol, x_f64, xoff, woff;  // xoff: first entry of this child's columns in a gathered row; woff: of its W in the LDS copy
+    int order, radial, ldw;  // POLY: powers 1 .. order; CENTRES: radial (1) or sigmoid (0), n = centres; ldw: row length of W in HBM
     const void *X;
     int64_t ldx;
-    const double *W;  // RFF: raw (d, n) row-major on the device
+    const double *W;  // RFF: raw (d, n) row-major on the device; CENTRES: C^T (d, ldw) -- the handle's float64 copy
 };
+
+// what a length-scale slot belongs to (SviArgs::lskind): decides the factor the features take per input dimension
+// (svi_ls_scale) and the power of l the summed gradient is divided by (svi_ls_grad)
+#define SVI_LS_RFF 0
+#define SVI_LS_RADIAL 1
+#define SVI_LS_SIGMOID 2
 
 struct SviArgs {
     const SviChild *kid;  // the children's table in device memory (uniform loads; not in the kernel arguments, which would
@@ -55,6 +66,7 @@ struct SviArgs {
     int64_t np, N;
     const void *y, *rowarg;
     const double *lconst;  // per row: the f-independent part of loglike (log-factorial terms), or null
+    const int *lskind;     // per length-scale slot: SVI_LS_* (n_ls entries, device; built at create time)
     const double *bias;    // per step of this launch: Adam's 1 - beta1^t, 1 - beta2^t (sgd.py:322-323)
     double *z, *s1, *s2;
     const double *lower, *upper;
@@ -93,6 +105,24 @@ __device__ __forceinline__ double svi_softplus(double f) { return fmax(f, 0.0) +
 __device__ __forceinline__ double svi_expit(double f) {
     const double e = exp(-fabs(f));
     return f >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+}
+
+// per input dimension, what a child's features multiply x (or x - c) by: 1 / (2 pi l) (random Fourier), 1 / (2 l^2) (radial:
+// X and C are divided by 2 l^2 BEFORE the squared distance, basis_functions.py:685-686), 1 / l (sigmoid, :784)
+__device__ __forceinline__ double svi_ls_scale(int kind, double l) {
+    if (kind == SVI_LS_RADIAL) return 1.0 / (2.0 * (l * l));
+    if (kind == SVI_LS_SIGMOID) return 1.0 / l;
+    return 0.15915494309189533576888 / l;
+}
+
+// the summed contraction of a slot -> its gradient: the factor that depends on l alone, applied ONCE to the K components'
+// sum: 1 / l^2 (random Fourier; sigmoid, basis_functions.py:809-815), 1 / l^6 (radial, :712-719)
+__device__ __forceinline__ double svi_ls_grad(int kind, double sm2, double l) {
+    if (kind == SVI_LS_RADIAL) {
+        const double l2 = l * l;
+        return sm2 / (l2 * l2 * l2);
+    }
+    return sm2 / (1.0 * (l * l));
 }
 
 // d loglike / d f and the f-dependent part of loglike (Gaussian: the squared error)   likelihoods.py:46-104,171-233,298-368,456-521
@@ -179,7 +209,7 @@ struct SviLds {
     ldsd *xm, *xC, *xs;             // x of all coordinates: (F, K) means, (F, K) covariances, the ns shared coordinates
     ldsd *zc, *s1c, *s2c, *loc, *hic;  // this workgroup's column (2 F: means then covariances): z, updater state, bounds
     ldsd *zs, *s1s, *s2s, *los, *his;  // the shared coordinates (replicated in every workgroup)
-    ldsd *Phi, *dfs, *Q, *Xb, *yb, *nb, *Dr, *mk, *sk, *edm, *edc, *q, *logz, *alpha, *gls, *psc, *red, *misc, *Wl, *ils, *Rc, *stage;
+    ldsd *Phi, *dfs, *Q, *Xb, *yb, *nb, *Dr, *mk, *sk, *edm, *edc, *q, *logz, *alpha, *gls, *psc, *red, *misc, *Wl, *ils, *Rc, *stage, *lsk;
     ldsf *Ef;                       // the draws of this component's samples (L, F)
     ldsb *lg;                       // is_log of all np coordinates
 };
@@ -191,7 +221,7 @@ static __host__ __device__ size_t svi_lds_layout(const SviArgs &a, size_t *off) 
                           M * (size_t)a.dsum, M, M, M, F, F, F, F, (size_t)a.K * a.K, (size_t)a.K, (size_t)a.K,
                           (size_t)(a.n_ls > 0 ? a.n_ls : 1), (size_t)a.K * (a.n_ls + 4), (size_t)SVI_WAVES, 8,
                           (size_t)a.wtot, (size_t)(a.n_ls > 0 ? a.n_ls : 1), (size_t)a.nkids, (size_t)(a.K + a.n_ls + 4),
-                          ((size_t)a.L * F * 4 + 7) / 8, ((size_t)a.np + 7) / 8};
+                          (size_t)(a.n_ls > 0 ? a.n_ls : 1), ((size_t)a.L * F * 4 + 7) / 8, ((size_t)a.np + 7) / 8};
     size_t o = 0;
     for (size_t i = 0; i < sizeof(cnt) / sizeof(cnt[0]); ++i) {
         if (off) off[i] = o;
@@ -214,6 +244,7 @@ __device__ __forceinline__ SviLds svi_carve(double *sm, const SviArgs &a) {
     s.q = b + off[i++]; s.logz = b + off[i++]; s.alpha = b + off[i++]; s.gls = b + off[i++]; s.psc = b + off[i++];
     s.red = b + off[i++]; s.misc = b + off[i++];
     s.Wl = b + off[i++]; s.ils = b + off[i++]; s.Rc = b + off[i++]; s.stage = b + off[i++];
+    s.lsk = b + off[i++];   // SVI_LS_* per length-scale slot (as doubles: one carve for everything)
     s.Ef = (ldsf *)(b + off[i++]);
     s.lg = (ldsb *)(b + off[i++]);
     return s;
@@ -249,6 +280,18 @@ __device__ __forceinline__ void svi_gather_issue(const SviArgs &a, const int *id
     }
 }
 
+// launch start: the children's tables into LDS (s.Wl at woff) -- a random Fourier child's W (d, n), a centre child's C^T
+// (d, n) out of the handle's padded float64 copy (row length ldw); they live there for the whole launch
+__device__ __forceinline__ void svi_load_tables(const SviArgs &a, const SviLds &s) {
+    const int tid = threadIdx.x;
+    for (int c = 0; c < a.nkids; ++c) {
+        const SviChild &k = a.kid[c];
+        if (k.kind != RR_SGD_CHILD_RFF && k.kind != RR_SGD_CHILD_CENTRES) continue;
+        RR_DEV_ASSERT(k.woff >= 0 && k.woff + k.d * k.n <= a.wtot && k.ldw >= k.n);
+        for (int o = tid; o < k.d * k.n; o += SVI_THREADS) s.Wl[k.woff + o] = k.W[(size_t)(o / k.n) * k.ldw + o % k.n];
+    }
+}
+
 // c: Phi (M, F) in float64 from the gathered rows, the batch's loglike constant -> misc[0]
 __device__ __forceinline__ void svi_features(const SviArgs &a, const SviLds &s, const SviGather &g) {
     const int tid = threadIdx.x, M = a.M, tot = M * a.dsum;
@@ -268,6 +311,34 @@ __device__ __forceinline__ void svi_features(const SviArgs &a, const SviLds &s, 
             for (int e = tid; e < M * k.width; e += SVI_THREADS) {
                 const int r = e / k.width, j = e % k.width;
                 s.Phi[r * a.Fp + k.col0 + j] = (k.onescol && j == 0) ? 1.0 : s.Xb[r * a.dsum + k.xoff + j - k.onescol];
+            }
+        } else if (k.kind == RR_SGD_CHILD_POLY) {
+            // [1 | x_i^1 .. x_i^order per input column i] (basis_functions.py:549-561): powers by repeated multiplication
+            RR_DEV_ASSERT(k.width == k.onescol + k.d * k.order && k.col0 + k.width <= a.F && k.xoff + k.d <= a.dsum);
+            for (int e = tid; e < M * k.width; e += SVI_THREADS) {
+                const int r = e / k.width, j = e % k.width;
+                double v = 1.0;
+                if (!(k.onescol && j == 0)) {
+                    const int jj = j - k.onescol, i = jj / k.order, p = jj % k.order + 1;
+                    const double x = s.Xb[r * a.dsum + k.xoff + i];
+                    v = x;
+                    for (int q = 1; q < p; ++q) v *= x;
+                }
+                s.Phi[r * a.Fp + k.col0 + j] = v;
+            }
+        } else if (k.kind == RR_SGD_CHILD_CENTRES) {
+            // z = sum_i ((x_i - c_ji) s_i)^2 from the differences; radial: exp(-z), sigmoid: expit(sqrt(z)) (0.5 at z = 0)
+            RR_DEV_ASSERT(k.woff >= 0 && k.woff + k.d * k.n <= a.wtot && k.ls0 >= 0 && k.ls0 + k.n_ls <= a.n_ls &&
+                          k.col0 + k.n <= a.F && k.xoff + k.d <= a.dsum);
+            const ldsd *il = s.ils + k.ls0, *C = s.Wl + k.woff;
+            for (int e = tid; e < M * k.n; e += SVI_THREADS) {
+                const int r = e / k.n, j = e % k.n;
+                double z = 0.0;
+                for (int i = 0; i < k.d; ++i) {
+                    const double t = (s.Xb[r * a.dsum + k.xoff + i] - C[i * k.n + j]) * il[k.n_ls == 1 ? 0 : i];
+                    z = fma(t, t, z);
+                }
+                s.Phi[r * a.Fp + k.col0 + j] = k.radial ? exp(-z) : svi_expit(sqrt(z));
             }
         } else {
             const double scale = 1.0 / sqrt((double)k.n);
@@ -537,7 +608,7 @@ __device__ __forceinline__ void svi_form_x(const SviArgs &a, const SviLds &s, in
         s.mk[f] = s.xm[f * K + k];
         s.sk[f] = sqrt(s.xC[f * K + k]);
     }
-    for (int h = tid; h < a.n_ls; h += SVI_THREADS) s.ils[h] = 0.15915494309189533576888 / s.xs[ns - a.n_ls + h];
+    for (int h = tid; h < a.n_ls; h += SVI_THREADS) s.ils[h] = svi_ls_scale((int)s.lsk[h], s.xs[ns - a.n_ls + h]);
     svi_child_sums(a, s);   // -> s.Rc
     svi_sync();
 }
@@ -569,9 +640,8 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
         s.his[p] = a.upper[2 * fk + p];
     }
     for (int p = tid; p < (int)a.np; p += SVI_THREADS) s.lg[p] = a.islog[p];
-    for (int c = 0; c < nk; ++c)
-        if (a.kid[c].kind == RR_SGD_CHILD_RFF)
-            for (int o = tid; o < a.kid[c].d * a.kid[c].n; o += SVI_THREADS) s.Wl[a.kid[c].woff + o] = a.kid[c].W[o];
+    for (int h = tid; h < a.n_ls; h += SVI_THREADS) s.lsk[h] = (double)a.lskind[h];
+    svi_load_tables(a, s);
     SviGather gth;
     svi_gather_issue(a, a.idx, gth);
     svi_sync();
@@ -619,20 +689,36 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
             s.edc[j] = ac / (L * s.sk[j]);
         }
         // -(EdPhi o dPhi_i).sum() of this component: W[i, :] . T[i, :] / l_i^2 with T = X^T (E_s o P_c - E_c o P_s); the
-        // isotropic parameter takes input dimension 0 only, as the reference does (basis_functions.py:896)
+        // isotropic parameter takes input dimension 0 only, as the reference does (basis_functions.py:896).  A centre child's
+        // slots (rr_glm_svi_create_all) sit next to the random Fourier children's: one wave per slot either way
         for (int h = wave; h < a.n_ls; h += SVI_WAVES) {
             int c = 0;
-            while (!(a.kid[c].kind == RR_SGD_CHILD_RFF && h >= a.kid[c].ls0 && h < a.kid[c].ls0 + a.kid[c].n_ls)) ++c;
+            while (c + 1 < nk && !(h >= a.kid[c].ls0 && h < a.kid[c].ls0 + a.kid[c].n_ls)) ++c;   // the child that owns slot h
+            RR_DEV_ASSERT(h >= a.kid[c].ls0 && h < a.kid[c].ls0 + a.kid[c].n_ls && a.kid[c].ls0 + a.kid[c].n_ls <= a.n_ls &&
+                          a.kid[c].woff + (h - a.kid[c].ls0 + 1) * a.kid[c].n <= a.wtot);
             const SviChild &kd = a.kid[c];
             const int i = h - kd.ls0;
             const double sc = 1.0 / ((double)L * K);
             const ldsd *W = s.Wl + kd.woff + i * kd.n;
             double acc = 0.0;
-            for (int o = lane; o < M * kd.n; o += 64) {
-                const int r = o / kd.n, j = o % kd.n, jc = kd.col0 + j, js = jc + kd.n;
-                const double epc = (s.mk[jc] * s.Dr[r] + s.sk[jc] * s.Q[r * F + jc]) * sc;
-                const double eps = (s.mk[js] * s.Dr[r] + s.sk[js] * s.Q[r * F + js]) * sc;
-                acc = fma(W[j] * s.Xb[r * a.dsum + kd.xoff + i], eps * s.Phi[r * a.Fp + jc] - epc * s.Phi[r * a.Fp + js], acc);
+            if (kd.kind == RR_SGD_CHILD_CENTRES) {
+                // -sum_{r,j} EdPhi[r][j] dPhi_i[r][j] without the factor of l alone (phase i: 1 / l^6, 1 / l^2):
+                // radial dPhi_i l^6 = Phi (x_i - c_ji)^2; sigmoid dPhi_i l^2 = -|x_i - c_ji| Phi (1 - Phi) -- no division: a row
+                // on a centre gives 0
+                for (int o = lane; o < M * kd.n; o += 64) {
+                    const int r = o / kd.n, j = o % kd.n, jc = kd.col0 + j;
+                    const double ep = (s.mk[jc] * s.Dr[r] + s.sk[jc] * s.Q[r * F + jc]) * sc;
+                    const double df = s.Xb[r * a.dsum + kd.xoff + i] - W[j], ph = s.Phi[r * a.Fp + jc];
+                    const double u = kd.radial ? ph * (df * df) : -(fabs(df) * (ph * (1.0 - ph)));
+                    acc = fma(-ep, u, acc);
+                }
+            } else {
+                for (int o = lane; o < M * kd.n; o += 64) {
+                    const int r = o / kd.n, j = o % kd.n, jc = kd.col0 + j, js = jc + kd.n;
+                    const double epc = (s.mk[jc] * s.Dr[r] + s.sk[jc] * s.Q[r * F + jc]) * sc;
+                    const double eps = (s.mk[js] * s.Dr[r] + s.sk[js] * s.Q[r * F + js]) * sc;
+                    acc = fma(W[j] * s.Xb[r * a.dsum + kd.xoff + i], eps * s.Phi[r * a.Fp + jc] - epc * s.Phi[r * a.Fp + js], acc);
+                }
             }
             acc = svi_wave_sum(acc);
             if (lane == 0) s.gls[h] = acc;
@@ -720,8 +806,7 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
                 const int h = p - nk - a.n_lik;
                 double sm2 = 0.0;
                 for (int j = 0; j < K; ++j) sm2 += s.psc[j * npub + h];
-                const double l = s.xs[p];
-                g = sm2 / (1.0 * (l * l));
+                g = svi_ls_grad((int)s.lsk[h], sm2, s.xs[p]);
             }
             if (s.lg[2 * fk + p]) g *= s.xs[p];
             n2s = g * g;
@@ -786,10 +871,8 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_starts_kernel(const Sv
         s.xC[p] = x[fk + p];
     }
     for (int p = tid; p < ns; p += SVI_THREADS) s.xs[p] = x[2 * fk + p];
-    for (int ch = 0; ch < nk; ++ch)
-        if (a.kid[ch].kind == RR_SGD_CHILD_RFF)
-            for (int o = tid; o < a.kid[ch].d * a.kid[ch].n; o += SVI_THREADS) s.Wl[a.kid[ch].woff + o] = a.kid[ch].W[o];
-    for (int h = tid; h < a.n_ls; h += SVI_THREADS) s.ils[h] = 0.15915494309189533576888 / x[2 * fk + ns - a.n_ls + h];
+    svi_load_tables(a, s);
+    for (int h = tid; h < a.n_ls; h += SVI_THREADS) s.ils[h] = svi_ls_scale(a.lskind[h], x[2 * fk + ns - a.n_ls + h]);
     svi_sync();
     svi_features(a, s, gth);
     const double ivar = a.n_lik ? 1.0 / s.xs[nk] : 0.0;
@@ -837,6 +920,7 @@ struct rr_glm_svi {
     double *cand = nullptr, *out = nullptr;
     size_t cand_cap = 0;
     long long *prof = nullptr;
+    int *lskind = nullptr;   // SviArgs::lskind
 };
 
 static void svi_free(rr_glm_svi *o) {
@@ -844,7 +928,7 @@ static void svi_free(rr_glm_svi *o) {
     if (o->dkid) (void)hipFree(o->dkid);
     if (o->dbias) (void)hipFree(o->dbias);
     void *q[] = {o->a.z, o->a.s1, o->a.s2, o->lower, o->upper, o->islog, o->a.pubcol, o->a.pubrow, o->a.pubsc, o->a.bar,
-                 o->a.objs, o->a.norms, o->cand, o->out};
+                 o->a.objs, o->a.norms, o->cand, o->out, o->lskind};
     for (void *v : q)
         if (v) (void)hipFree(v);
     for (double *w : o->dW)
@@ -854,7 +938,9 @@ static void svi_free(rr_glm_svi *o) {
 
 extern "C" {
 
-int rr_glm_svi_supported(int F, int K, int L, int M, int n_children, int dsum, int n_ls) {
+// table_entries: the doubles of all W and centre tables held in LDS
+static int svi_supported(int F, int K, int L, int M, int n_children, int dsum, int n_ls, int64_t table_entries) {
+    if (table_entries < 0 || table_entries > (1 << 20) || dsum < 0 || n_ls < 0) return 0;
     if (F < 1 || K < 1 || K > SVI_MAXK || L < 1 || M < 1 || n_children < 1 || n_children > SVI_MAXCHILD) return 0;
     if (F < n_children || M > SVI_THREADS || n_children + 1 + n_ls > SVI_THREADS) return 0;
     SviArgs a;
@@ -864,32 +950,42 @@ int rr_glm_svi_supported(int F, int K, int L, int M, int n_children, int dsum, i
     // state fits the CU's LDS
     if ((int64_t)L * M * F > (int64_t)1 << 20 || (int64_t)M * F > 8192 || (int64_t)M * dsum > SVI_GREG * SVI_THREADS) return 0;
     a.np = 2 * (int64_t)F * K + a.ns;
-    a.wtot = dsum * (F / 2 + 1);  // (an upper bound of sum d_c n_c: the children's frequency matrices, kept in LDS)
+    a.wtot = (int)table_entries;
     return svi_lds_doubles(a) * 8 <= 150 * 1024 ? 1 : 0;
 }
 
-int rr_glm_svi_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
-                      const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K, int L,
-                      int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper, const unsigned char *is_log,
-                      int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_svi **out) {
+int rr_glm_svi_supported(int F, int K, int L, int M, int n_children, int dsum, int n_ls) {
+    // (an upper bound of sum d_c n_c: the children's frequency matrices, kept in LDS)
+    return svi_supported(F, K, L, M, n_children, dsum, n_ls, (int64_t)dsum * (F / 2 + 1));
+}
+
+int rr_glm_svi_supported_all(int F, int K, int L, int M, int n_children, int dsum, int n_ls, int table_entries) {
+    return svi_supported(F, K, L, M, n_children, dsum, n_ls, table_entries);
+}
+
+static int svi_create(bool all, const char *who, rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX,
+                      const int *x_dtype, const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst,
+                      int dtype, int K, int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
+                      const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_svi **out) {
     RR_REQUIRE(ctx != nullptr && children != nullptr && dX != nullptr && x_dtype != nullptr && ldx != nullptr && dy != nullptr &&
                z0 != nullptr && lower != nullptr && upper != nullptr && is_log != nullptr && upd_par != nullptr && out != nullptr,
-               "rr_glm_svi_create: null argument");
+               "%s: null argument", who);
     *out = nullptr;
-    RR_REQUIRE(n_children >= 1 && n_children <= SVI_MAXCHILD, "rr_glm_svi_create: 1 <= children <= %d", SVI_MAXCHILD);
-    RR_REQUIRE(K >= 1 && K <= SVI_MAXK && L >= 1 && M >= 1 && N >= 1, "rr_glm_svi_create: bad K, L, minibatch or N");
+    RR_REQUIRE(n_children >= 1 && n_children <= SVI_MAXCHILD, "%s: 1 <= children <= %d", who, SVI_MAXCHILD);
+    RR_REQUIRE(K >= 1 && K <= SVI_MAXK && L >= 1 && M >= 1 && N >= 1, "%s: bad K, L, minibatch or N", who);
     RR_REQUIRE(lik >= RR_LIK_BERNOULLI && lik <= RR_LIK_POISSON_SOFTPLUS && (lik == RR_LIK_GAUSSIAN) == (n_lik == 1),
-               "rr_glm_svi_create: likelihood %d with %d likelihood parameter(s)", lik, n_lik);
-    RR_REQUIRE((lik == RR_LIK_BINOMIAL) == (drowarg != nullptr), "rr_glm_svi_create: the per-row argument goes with the binomial likelihood");
-    RR_REQUIRE(updater >= RR_UPD_SGD && updater <= RR_UPD_ADAM, "rr_glm_svi_create: unknown updater %d", updater);
-    RR_REQUIRE(maxiter >= 1 && maxiter < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), "rr_glm_svi_create: bad maxiter / N");
-    RR_REQUIRE(dtype == RR_F32 || dtype == RR_F64, "rr_glm_svi_create: bad dtype");
+               "%s: likelihood %d with %d likelihood parameter(s)", who, lik, n_lik);
+    RR_REQUIRE((lik == RR_LIK_BINOMIAL) == (drowarg != nullptr), "%s: the per-row argument goes with the binomial likelihood", who);
+    RR_REQUIRE(updater >= RR_UPD_SGD && updater <= RR_UPD_ADAM, "%s: unknown updater %d", who, updater);
+    RR_REQUIRE(maxiter >= 1 && maxiter < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), "%s: bad maxiter / N", who);
+    RR_REQUIRE(dtype == RR_F32 || dtype == RR_F64, "%s: bad dtype", who);
     RR_CHECK_HIP(hipSetDevice(ctx->device));
     rr_glm_svi *o = new rr_glm_svi();
     o->ctx = ctx;
     SviArgs &a = o->a;
     memset(&a, 0, sizeof a);
     int col = 0, nls = 0, xoff = 0, woff = 0;
+    std::vector<int> lskind;
     for (int s = 0; s < n_children; ++s) {
         const rr_glm_sgd_child &k = children[s];
         SviChild &c = o->hkid[s];
@@ -913,43 +1009,76 @@ int rr_glm_svi_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *child
                     (void)hipGetLastError();
                     if (w) (void)hipFree(w);
                     svi_free(o);
-                    rr_set_error("rr_glm_svi_create: device allocation failed");
+                    rr_set_error("%s: device allocation failed", who);
                     return RR_ERR_OOM;
                 }
                 o->dW.push_back(w);
                 c.W = w;
+                c.ldw = b->n;
             }
         } else if (ok && k.kind == RR_SGD_CHILD_LINEAR) {
             ok = k.d >= 1 && k.n_ls == 0;
             c.d = k.d; c.n = 0; c.n_ls = 0; c.onescol = k.onescol ? 1 : 0; c.width = k.d + c.onescol;
+        } else if (ok && all && k.kind == RR_SGD_CHILD_CENTRES) {
+            int Mc = 0, Mp = 0, radial = 0;
+            const double *Ct = nullptr;
+            if (!rr_centres_svi_child(k.basis, ctx, k.n_ls, &Mc, &Mp, &radial, &Ct)) {
+                svi_free(o);
+                rr_set_error("%s: child %d: a centres basis (rr_centres_create) of this context with 1 or Xdim length scales", who, s);
+                return RR_ERR_INVALID;
+            }
+            c.d = k.basis->d; c.n = Mc; c.n_ls = k.n_ls; c.width = Mc; c.onescol = 0; c.radial = radial; c.ldw = Mp; c.W = Ct;
+        } else if (ok && all && k.kind == RR_SGD_CHILD_POLY) {
+            if (!(k.d >= 1 && k.order >= 0 && (k.order >= 1 || k.onescol) && k.n_ls == 0 && (int64_t)k.d * k.order < (1 << 20))) {
+                svi_free(o);
+                rr_set_error("%s: child %d: a polynomial child needs d >= 1 columns, order >= 0 and at least one feature (d=%d order=%d "
+                             "include_bias=%d)", who, s, k.d, k.order, k.onescol);
+                return RR_ERR_INVALID;
+            }
+            c.d = k.d; c.n = 0; c.n_ls = 0; c.onescol = k.onescol ? 1 : 0; c.order = k.order; c.width = c.onescol + k.d * k.order;
         } else {
             ok = false;
         }
-        if (k.kind == RR_SGD_CHILD_CENTRES || k.kind == RR_SGD_CHILD_POLY) {  // (rr_glm_sgd_step's kinds only)
+        if (!all && (k.kind == RR_SGD_CHILD_CENTRES || k.kind == RR_SGD_CHILD_POLY)) {  // (rr_glm_svi_create_all takes them)
             svi_free(o);
-            rr_set_error("rr_glm_svi_create: child %d: centre and polynomial children (kind %d) are not taken by the fused loop", s, k.kind);
+            rr_set_error("%s: child %d: centre and polynomial children (kind %d) are not taken by the fused loop", who, s, k.kind);
+            return RR_ERR_INVALID;
+        }
+        if (k.kind == RR_SGD_CHILD_GM) {
+            svi_free(o);
+            rr_set_error("%s: child %d: a spectral-mixture child (RR_SGD_CHILD_GM) is not taken by the fused loop", who, s);
             return RR_ERR_INVALID;
         }
         if (!ok) {
             svi_free(o);
-            rr_set_error("rr_glm_svi_create: child %d: a random Fourier basis of this context with 1 or Xdim length scales, or a "
-                         "linear child with d >= 1 columns, and its resident rows", s);
+            rr_set_error("%s: child %d: a random Fourier basis of this context with 1 or Xdim length scales, or a "
+                         "linear child with d >= 1 columns, and its resident rows", who, s);
             return RR_ERR_INVALID;
         }
+        for (int h = 0; h < c.n_ls; ++h)
+            lskind.push_back(c.kind == RR_SGD_CHILD_RFF ? SVI_LS_RFF : (c.radial ? SVI_LS_RADIAL : SVI_LS_SIGMOID));
         col += c.width;
         nls += c.n_ls;
         xoff += c.d;
-        if (c.kind == RR_SGD_CHILD_RFF) woff += c.d * c.n;
+        if (c.kind == RR_SGD_CHILD_RFF || c.kind == RR_SGD_CHILD_CENTRES) {
+            if ((int64_t)woff + (int64_t)c.d * c.n > (1 << 20)) {   // (far beyond one CU's LDS; keeps the offsets in int)
+                svi_free(o);
+                rr_set_error("%s: child %d: the children's tables are outside the fused small-batch loop's range", who, s);
+                return RR_ERR_UNSUPPORTED;
+            }
+            woff += c.d * c.n;
+        }
     }
     a.nkids = n_children; a.F = col; a.Fp = col | 1; a.K = K; a.L = L; a.M = M; a.lik = lik; a.n_lik = n_lik; a.n_ls = nls;
     a.ns = n_children + n_lik + nls; a.updater = updater; a.y_f64 = dtype == RR_F64; a.dsum = xoff; a.N = N; a.wtot = woff;
     a.np = 2 * (int64_t)col * K + a.ns;
     a.y = dy; a.rowarg = drowarg; a.lconst = dlconst; a.bmag = bmag;
     for (int i = 0; i < 4; ++i) a.up[i] = upd_par[i];
-    if (!rr_glm_svi_supported(a.F, K, L, M, n_children, a.dsum, nls)) {
+    if (!(all ? rr_glm_svi_supported_all(a.F, K, L, M, n_children, a.dsum, nls, woff)
+              : rr_glm_svi_supported(a.F, K, L, M, n_children, a.dsum, nls))) {
         svi_free(o);
-        rr_set_error("rr_glm_svi_create: F = %d, K = %d, nsamples = %d, minibatch = %d is outside the fused small-batch loop's range "
-                     "(rr_glm_svi_supported)", a.F, K, L, M);
+        rr_set_error("%s: F = %d, K = %d, nsamples = %d, minibatch = %d is outside the fused small-batch loop's range "
+                     "(rr_glm_svi_supported%s)", who, a.F, K, L, M, all ? "_all" : "");
         return RR_ERR_UNSUPPORTED;
     }
     o->lds_bytes = svi_lds_doubles(a) * 8;
@@ -968,6 +1097,8 @@ int rr_glm_svi_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *child
     if (e == hipSuccess) e = hipMalloc((void **)&a.pubrow, (size_t)2 * K * K * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&a.pubsc, (size_t)2 * K * npub * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&a.bar, 64);
+    if (e == hipSuccess) e = hipMalloc((void **)&o->lskind, (lskind.size() + 1) * sizeof(int));
+    if (e == hipSuccess && !lskind.empty()) e = hipMemcpy(o->lskind, lskind.data(), lskind.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc((void **)&a.objs, (size_t)maxiter * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&a.norms, (size_t)maxiter * 8);
     if (e == hipSuccess) e = hipMemcpy(a.z, z0, nb, hipMemcpyHostToDevice);
@@ -984,16 +1115,33 @@ int rr_glm_svi_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *child
     if (e != hipSuccess) {
         (void)hipGetLastError();
         svi_free(o);
-        rr_set_error("rr_glm_svi_create: %s", hipGetErrorString(e));
+        rr_set_error("%s: %s", who, hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP;
     }
-    a.lower = o->lower; a.upper = o->upper; a.islog = o->islog; a.kid = o->dkid;
+    a.lower = o->lower; a.upper = o->upper; a.islog = o->islog; a.kid = o->dkid; a.lskind = o->lskind;
     if (getenv("RR_SVI_PROF")) {
         if (hipMalloc((void **)&o->prof, 16 * sizeof(long long)) == hipSuccess) (void)hipMemset(o->prof, 0, 16 * sizeof(long long));
         a.prof = o->prof;
     }
     *out = o;
     return RR_OK;
+}
+
+int rr_glm_svi_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                      const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K, int L,
+                      int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper, const unsigned char *is_log,
+                      int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_svi **out) {
+    return svi_create(false, "rr_glm_svi_create", ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dlconst, dtype, K, L, M, lik,
+                      n_lik, z0, lower, upper, is_log, updater, upd_par, maxiter, bmag, out);
+}
+
+int rr_glm_svi_create_all(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                          const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K,
+                          int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
+                          const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
+                          rr_glm_svi **out) {
+    return svi_create(true, "rr_glm_svi_create_all", ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dlconst, dtype, K, L, M,
+                      lik, n_lik, z0, lower, upper, is_log, updater, upd_par, maxiter, bmag, out);
 }
 
 int rr_glm_svi_set_start(rr_glm_svi *o, const double *z0, const double *lower, const double *upper, const unsigned char *is_log) {

@@ -140,12 +140,18 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         three as well (float32 bases of Xdim <= 4096 with a scalar or (d,) length scale; above 128 columns the centre bases'
         kernels walk the dimensions in blocks, and only under "all" are such bases resident at all): their features come from the length
         scales in HBM and their gradient's sums are reduced there.  Such a fit takes the step-per-call loop at every minibatch
-        size -- the many-steps-per-launch kernel of small minibatches (rr_svi.hip) does not hold these children.  Any other
-        value: ValueError at ``fit``."""
+        size unless ``fused_bases="all"`` says otherwise.  Any other value: ValueError at ``fit``.
+    fused_bases : "fourier" (default) | "all"
+        Which children the many-steps-per-launch kernel of small minibatches (rr_svi.hip: the reference's default shape, 10
+        rows per step) takes.  "fourier": random Fourier, FastFoodRBF and linear children, as before.  "all" (needs
+        ``resident_bases="all"``; ValueError at ``fit`` otherwise): RadialBasis, SigmoidalBasis and PolynomialBasis children
+        too -- their features and the length scales' gradient are formed inside that kernel in float64 -- whenever the shape
+        is in its range (rr_glm_svi_supported_all); a FastFoodGM child, a shape outside the range or several ranks keep the
+        step-per-call loop.  Any other value: ValueError at ``fit``."""
 
     def __init__(self, likelihood=Gaussian(), basis=LinearBasis(), K=10, maxiter=3000, batch_size=10, updater=None,
                  nsamples=50, nstarts=500, random_state=None, sampler="host", distributed=False, gram_engine=None,
-                 devices=None, predict_engine="host", resident_bases="fourier"):
+                 devices=None, predict_engine="host", resident_bases="fourier", fused_bases="fourier"):
         self.likelihood = likelihood
         self.basis = basis
         self.K = K
@@ -161,6 +167,7 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         self.devices = devices          # several GPUs behind this call, in this process (see StandardLinearModel; multigpu.py)
         self.predict_engine = predict_engine
         self.resident_bases = resident_bases
+        self.fused_bases = fused_bases
         self.random_ = check_random_state(self.random_state)
 
     def fit(self, X, y, likelihood_args=()):
@@ -185,6 +192,10 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         self._device_predictions()   # (validates predict_engine)
         if getattr(self, "resident_bases", "fourier") not in ("fourier", "all"):
             raise ValueError("resident_bases must be 'fourier' or 'all'")
+        if getattr(self, "fused_bases", "fourier") not in ("fourier", "all"):
+            raise ValueError("fused_bases must be 'fourier' or 'all'")
+        if getattr(self, "fused_bases", "fourier") == "all" and getattr(self, "resident_bases", "fourier") != "all":
+            raise ValueError("fused_bases='all' needs resident_bases='all'")
         self._drop_serving()
         self._dev_seed = None  # the device sampler is re-keyed from random_ per fit
         N, _ = X.shape
@@ -418,14 +429,22 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         kids, n_lik = feats._kids, self._n_lik(params)
         # small minibatches (the reference's default is 10 rows): the whole loop inside one kernel, many steps per launch
         # (not between ranks: that kernel has no exchange step)
+        every = getattr(self, "fused_bases", "fourier") == "all"   # centre and polynomial children in that kernel too
+        taken = ("rff", "linear", "centres", "poly") if every else ("rff", "linear")
         if self._fused_sgd and os.environ.get("RR_GLM_FUSED", "1") != "0" and y is not None and len(likelihood_args) <= 1 \
-                and np.isfinite(self.maxiter) and comm is None and all(c[0] in ("rff", "linear") for c in children):
+                and np.isfinite(self.maxiter) and comm is None and all(c[0] in taken for c in children):
             N = len(y)
             M = int(min(self.batch_size, N))
             F = int(self.D_)
-            dsum = sum((kid.W.shape[0] if c[0] == "rff" else c[1]) for kid, c in zip(kids, children))
-            n_ls = sum(c[2] for c in children if c[0] == "rff")
-            if _hip.svi_supported(F, self.K, self.nsamples, M, len(children), dsum, n_ls):
+            width = {"rff": lambda kid, c: kid.W.shape[0], "centres": lambda kid, c: c[1].d}   # (linear, poly: c[1] columns)
+            dsum = sum(width.get(c[0], lambda kid, c: c[1])(kid, c) for kid, c in zip(kids, children))
+            n_ls = sum(c[2] for c in children if c[0] in ("rff", "centres"))
+            if every:   # the tables the kernel keeps in LDS, counted exactly: W (Xdim, n) and centres (Xdim, M)
+                tables = sum(kid.W.shape[0] * c[1].n if c[0] == "rff" else (c[1].d * c[1].M if c[0] == "centres" else 0)
+                             for kid, c in zip(kids, children))
+                if _hip.svi_supported_all(F, self.K, self.nsamples, M, len(children), dsum, n_ls, tables):
+                    return _FusedLoop(self, feats, n_lik, children, y, likelihood_args, all_children=True)
+            elif _hip.svi_supported(F, self.K, self.nsamples, M, len(children), dsum, n_ls):
                 return _FusedLoop(self, feats, n_lik, children, y, likelihood_args)
         return _ResidentLoop(self, feats, n_lik, children, comm=comm)
 
@@ -1085,9 +1104,10 @@ class _FusedLoop(object):
     BLOCK_BYTES = 48 << 20    # draws uploaded per launch at most (two device buffers of this size in turn)
     BLOCK_STEPS = 256
 
-    def __init__(self, glm, feats, n_lik, children, y, likelihood_args):
+    def __init__(self, glm, feats, n_lik, children, y, likelihood_args, all_children=False):
         from . import optimize as opt
         self.glm, self.feats, self.n_lik, self.children = glm, feats, n_lik, children
+        self.all_children = all_children   # rr_glm_svi_create_all: centre and polynomial children too
         self.y, self.largs = np.asarray(y, dtype=float), tuple(likelihood_args)
         self.svi = None
         self.updater = opt.Adam() if glm.updater is None else glm.updater
@@ -1125,11 +1145,11 @@ class _FusedLoop(object):
         self.dlc = dev.upload_vector(lc, np.float64) if lc is not None else None
         kids = [c + (kid.dX,) for c, kid in zip(self.children, feats._kids)]
         F = int(g.D_)
-        self.np_ = 2 * F * g.K + len(kids) + self.n_lik + sum(c[2] for c in self.children if c[0] == "rff")
+        self.np_ = 2 * F * g.K + len(kids) + self.n_lik + sum(c[2] for c in self.children if c[0] in ("rff", "centres"))
         hold = np.zeros(self.np_)
         self.svi = _hip.FusedSvi(dev, kids, len(self.y), self.dy, self.dn, self.dlc, g.K, g.nsamples, self.M, lik, self.n_lik, hold,
                                  np.full(self.np_, -np.inf), np.full(self.np_, np.inf), np.zeros(self.np_, dtype=np.uint8),
-                                 _hip.UPDATER_IDS[kind], par, max(1, int(g.maxiter)), g.B_)
+                                 _hip.UPDATER_IDS[kind], par, max(1, int(g.maxiter)), g.B_, all_children=self.all_children)
         self.F = F
         return self.svi
 
@@ -1212,7 +1232,7 @@ class _FusedLoop(object):
         regs = list(x[o:o + nk])
         ls, q = [], o + nk + self.n_lik
         for c in self.children:
-            n = c[2] if c[0] == "rff" else 0
+            n = c[2] if c[0] in ("rff", "centres") else 0   # (a polynomial child's c[2] is its include_bias)
             if n:
                 ls.append(x[q] if n == 1 else x[q:q + n])
             q += n

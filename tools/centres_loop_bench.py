@@ -8,7 +8,9 @@ Shapes: "large" -- N = 100 000, d = 8, M = 512 centres + a linear child, batch =
 "default" -- the reference's default regime (glm.py:120-124), batch = 10, maxiter = 3000, K = 10, L = 50, on 2000 rows,
 d = 2, M = 20.  nstarts = 0 in both: the loops are what is timed.  Per arm: wall time of `fit` / maxiter, and for the resident
 loop the median interval of `_resident_clock` (the host times at which steps were queued: the queue is two deep, so it
-follows the device's pace).  One JSON line per (shape, sampler) at the end."""
+follows the device's pace).  The "default" shape has a third arm, ``resident_bases="all", fused_bases="all"``: the
+many-steps-per-launch kernel of small minibatches (rr_svi.hip) with the centres child inside it; it raises if that loop was
+not taken.  One JSON line per (shape, sampler) at the end."""
 import argparse
 import json
 import os
@@ -19,6 +21,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import revrand_amd.basis_functions as bs  # noqa: E402
+from revrand_amd import _hip  # noqa: E402
 from revrand_amd import likelihoods as lk  # noqa: E402
 from revrand_amd.btypes import Parameter, Positive  # noqa: E402
 from revrand_amd.glm import GeneralizedLinearModel  # noqa: E402
@@ -34,13 +37,30 @@ def one_fit(shape, sampler, arm):
     y = np.sin(X[:, 0]) + 0.3 * X[:, 1] + 0.1 * rs.randn(s["N"])
     basis = bs.RadialBasis(centres=X[:s["M"]].copy(), lenscale=Parameter(np.ones(s["d"]), Positive())) + bs.LinearBasis(onescol=True)
     glm = GeneralizedLinearModel(lk.Gaussian(), basis, K=s["K"], nsamples=s["L"], batch_size=s["batch"], maxiter=s["maxiter"],
-                                 nstarts=0, random_state=1, sampler=sampler, resident_bases=arm)
+                                 nstarts=0, random_state=1, sampler=sampler, resident_bases="all" if arm == "fused" else arm,
+                                 fused_bases="all" if arm == "fused" else "fourier")
     np.random.seed(0)
-    t0 = time.perf_counter()
-    glm.fit(X, y)
-    wall = time.perf_counter() - t0
+    fused_steps = [0]
+    real_run = _hip.FusedSvi.run
+
+    def run(self, n, *a, **k):
+        fused_steps[0] += n
+        return real_run(self, n, *a, **k)
+    _hip.FusedSvi.run = run
+    try:
+        t0 = time.perf_counter()
+        glm.fit(X, y)
+        wall = time.perf_counter() - t0
+    finally:
+        _hip.FusedSvi.run = real_run
     out = {"wall_ms_per_step": 1e3 * wall / s["maxiter"]}
     ck = glm.__dict__.pop("_resident_clock", None)
+    if arm == "fused":
+        if fused_steps[0] != s["maxiter"]:
+            raise RuntimeError("fused_bases='all' did not take the fused loop (%d of %d steps)" % (fused_steps[0], s["maxiter"]))
+        return out
+    if fused_steps[0]:
+        raise RuntimeError("resident_bases=%r took the fused loop" % arm)
     if arm == "all":
         if ck is None:
             raise RuntimeError("resident_bases='all' did not take the resident loop")
@@ -59,17 +79,26 @@ def main():
     a = ap.parse_args()
     for shape in a.shapes.split(","):
         for sampler in a.samplers.split(","):
-            runs = {"fourier": [], "all": []}
-            one_fit(shape, sampler, "all")   # (first use: handles, buffers, the library's lazy allocations)
+            arms = ("fourier", "all", "fused") if shape == "default" else ("fourier", "all")
+            runs = {arm: [] for arm in arms}
+            for arm in arms[1:]:
+                one_fit(shape, sampler, arm)   # (first use: handles, buffers, the library's lazy allocations)
             for _ in range(a.reps):
-                for arm in ("fourier", "all"):
+                for arm in arms:
                     runs[arm].append(one_fit(shape, sampler, arm))
             best = {arm: min(r["wall_ms_per_step"] for r in runs[arm]) for arm in runs}
             clock = [r["clock_ms_per_step"] for r in runs["all"] if "clock_ms_per_step" in r]
-            print(json.dumps({"tool": "centres_loop_bench", "shape": dict(SHAPES[shape], name=shape), "sampler": sampler,
-                              "host_loop_ms_per_step": round(best["fourier"], 4), "resident_loop_ms_per_step": round(best["all"], 4),
-                              "resident_clock_ms_per_step": round(min(clock), 4) if clock else None,
-                              "speedup": round(best["fourier"] / best["all"], 2), "runs": runs}), flush=True)
+            line = {"tool": "centres_loop_bench", "shape": dict(SHAPES[shape], name=shape), "sampler": sampler,
+                    "host_loop_ms_per_step": round(best["fourier"], 4), "resident_loop_ms_per_step": round(best["all"], 4),
+                    "resident_clock_ms_per_step": round(min(clock), 4) if clock else None,
+                    "speedup": round(best["fourier"] / best["all"], 2)}
+            if "fused" in best:
+                # (repetition by repetition: the fused arm is faster than the step-per-call arm only if it is in EVERY pair)
+                line["fused_loop_ms_per_step"] = round(best["fused"], 4)
+                line["fused_faster_in_every_rep"] = all(f["wall_ms_per_step"] < r["wall_ms_per_step"]
+                                                        for f, r in zip(runs["fused"], runs["all"]))
+            line["runs"] = runs
+            print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
