@@ -530,6 +530,16 @@ void rr_glm_sgd_destroy(rr_glm_sgd *s);
  * tables held in LDS, sum over the random Fourier children of Xdim x n plus sum over the centre children of Xdim x centres
  * (rr_glm_svi_supported bounds it by dsum (F / 2 + 1), which holds for random Fourier children only).  The minibatch's rows
  * are held in registers between their loads and their use: minibatch x dsum <= 1024 bounds the input width.
+ * rr_glm_svi_create_gm -- same arguments, same object again -- takes every child rr_glm_svi_create_all takes plus
+ * RR_SGD_CHILD_GM: basis = the dense random Fourier equivalent of the component's chain (an RR_KIND_RFF handle of `ctx`, Xdim <= 128,
+ * n frequencies), n_ls = 2 Xdim.  Its raw W = V (Xdim, n) sits in LDS with the other tables; per row and frequency the kernel forms
+ * a = x . (V[:, j] / l) and, once per row, b = x . mean (in revolutions), and writes cos(a + b) | sin(a + b) | cos(a - b) | sin(a - b)
+ * scaled by 1 / sqrt(2 n) at 4 n columns -- the reference's column order (basis_functions.py:1471-1473).  The child owns 2 Xdim
+ * consecutive slots [mean | length scales] of the z layout above; with T+- = X^T (E_s o P_c - E_c o P_s) over the +- block the
+ * gradients are -(T+ - T-)[i] (a mean: may be zero or negative, never in log space, no division by it) and
+ * sum_j V[i][j] (t+ + t-)[i][j] / l_i^2 (a length scale).  Any other basis, another context's handle, Xdim > 128 or
+ * n_ls != 2 Xdim: RR_ERR_INVALID with a message naming the child.  rr_glm_svi_supported_gm is its range check; table_entries
+ * counts a GM child's Xdim x n as it counts a random Fourier child's.
  * dX[c], x_dtype[c], ldx[c]: child c's RESIDENT rows of its columns of X (all N rows, device); dy / drowarg: targets and the
  * binomial's n for all N rows (device, dtype); dlconst: per row, the part of loglike that does not depend on f (device float64:
  * Poisson -lgamma(y + 1), binomial lgamma(n + 1) - lgamma(y + 1) - lgamma(n - y + 1); NULL: zero -- Bernoulli, Gaussian);
@@ -547,6 +557,12 @@ int rr_glm_svi_create_all(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *c
                           int K, int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
                           const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
                           rr_glm_svi **out);
+int rr_glm_svi_supported_gm(int F, int K, int L, int M, int n_children, int dsum, int n_ls, int table_entries);
+int rr_glm_svi_create_gm(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                         const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype,
+                         int K, int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
+                         const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
+                         rr_glm_svi **out);
 /* The start point (structured_sgd picks it after the random starts, decorators.py:223-234), the bounds and the log-space
  * flags as logtrick_sgd leaves them (decorators.py:586-616), before the first step; NULL: unchanged. */
 int rr_glm_svi_set_start(rr_glm_svi *s, const double *z0, const double *lower, const double *upper, const unsigned char *is_log);
@@ -711,6 +727,12 @@ int rr_fastfood_gm_transform_dev(rr_basis *fastfood, const void *dX, int x_dtype
                                  const double *lenscale, int n_ls, void *dPhi, int out_dtype, int64_t ldphi);
 int rr_featmat_put_fastfood_gm(rr_featmat *fm, rr_basis *fastfood, const void *dX, int x_dtype, int64_t ldx,
                                const double *mean, const double *lenscale, int n_ls, int64_t col0);
+/* The same four blocks through the DENSE equivalent of the chain (basis: that RR_KIND_RFF handle, Xdim <= 128; dX in its
+ * rr_rff_padded layout; mean, lenscale: host, Xdim values each) at columns [col0, col0 + 4n): the random Fourier feature kernel
+ * twice, with every frequency moved by +- mean -- what rr_glm_sgd_step does for an RR_SGD_CHILD_GM child.  No lower limit on
+ * Xdim (the chain's mixture mode serves block sizes 16 .. 256 only).  Asynchronous on the context's stream. */
+int rr_featmat_put_gm(rr_featmat *fm, rr_basis *basis, const void *dX, int x_dtype, int64_t ldx, const double *mean,
+                      const double *lenscale, int64_t col0);
 
 /* mathfun.linalg.hadamard (mathfun/linalg.py:182-236): natural-order Walsh-Hadamard transform of each
  * row of host Y (rows, n), n = 2^p <= 4096, normalised by 1/n; ordering != 0 applies the sequency

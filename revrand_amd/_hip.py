@@ -202,6 +202,12 @@ SIGNATURES = {
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                              ctypes.c_int64, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]),
+    "rr_glm_svi_supported_gm": (ctypes.c_int, [ctypes.c_int] * 8),
+    "rr_glm_svi_create_gm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_int64, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]),
     "rr_glm_svi_set_start": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rr_glm_svi_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                       ctypes.c_uint64]),
@@ -266,6 +272,8 @@ SIGNATURES = {
                                                     ctypes.c_int64]),
     "rr_featmat_put_fastfood_gm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
+    "rr_featmat_put_gm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     "rr_hadamard": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                    ctypes.c_int, ctypes.c_void_p]),
     "rr_rff_gram_kernel_name": (ctypes.c_char_p, [ctypes.c_void_p]),
@@ -968,6 +976,17 @@ class FeatureMatrix(object):
         _check(self.lib, self.lib.rr_featmat_put_fastfood_gm(self.h, ff_handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld,
                                                              mu.ctypes.data_as(ctypes.c_void_p), lsp, nls, col0))
 
+    def put_gm(self, handle, dX, mean, lenscale, col0):
+        """FastFoodGM's four blocks of the rows dX through the DENSE equivalent of its chain (`handle`: that RffHandle, dX in
+        its padded layout; mean, lenscale: Xdim values each) into columns [col0, col0 + 4 n) (rr_featmat_put_gm): any Xdim <= 128,
+        asynchronous."""
+        mu = np.ascontiguousarray(mean, dtype=np.float64).ravel()
+        ls = np.ascontiguousarray(lenscale, dtype=np.float64).ravel()
+        if mu.size != handle.d or ls.size != handle.d:
+            raise ValueError("put_gm: mean and lenscale need Xdim = %d values each" % handle.d)
+        _check(self.lib, self.lib.rr_featmat_put_gm(self.h, handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld,
+                                                    mu.ctypes.data_as(ctypes.c_void_p), ls.ctypes.data_as(ctypes.c_void_p), col0))
+
     def download(self):
         """The rows of the last `begin` as they sit in HBM, (rows, ld) float32 with the padding columns (rr_featmat_download)."""
         out = np.empty((self.rows, (self.F + 255) // 256 * 256), dtype=np.float32)
@@ -1336,10 +1355,12 @@ class FusedSvi(object):
     rows (DeviceMatrix, all N rows); dy / drowarg: DeviceBuffers of all N targets / per-row arguments.  ResidentSgd's "centres"
     and "poly" tuples (+ dX) are passed on as they are: refused by the library's rr_glm_svi_create (the default), taken by
     rr_glm_svi_create_all (all_children=True), which forms their features and the length scales' gradient inside the kernel in
-    float64 (a "gm" child is refused by both)."""
+    float64; those two entry points both refuse a "gm" child.  gm_children=True selects a third, rr_glm_svi_create_gm, which
+    takes everything all_children takes plus ResidentSgd's ("gm", RffHandle of the component's dense equivalent, 2 Xdim, dX)
+    children."""
 
     def __init__(self, dev, children, N, dy, drowarg, dlconst, K, L, M, lik, n_lik, z0, lower, upper, is_log, updater_id, updater_par,
-                 maxiter, bmag, all_children=False):
+                 maxiter, bmag, all_children=False, gm_children=False):
         self.dev, self.lib, self.children = dev, dev.lib, list(children)
         self._keep = (dy, drowarg, dlconst)
         z0 = np.ascontiguousarray(z0, dtype=np.float64)
@@ -1368,6 +1389,8 @@ class FusedSvi(object):
         self.maxiter = int(maxiter)
         h = ctypes.c_void_p()
         create = self.lib.rr_glm_svi_create_all if all_children else self.lib.rr_glm_svi_create
+        if gm_children:
+            create = self.lib.rr_glm_svi_create_gm
         _check(self.lib, create(
             dev.ctx, nk, ctypes.cast(kids, ctypes.c_void_p), ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(dts, ctypes.c_void_p),
             ctypes.cast(lds, ctypes.c_void_p), int(N), _ptr(dy), _ptr(drowarg), _ptr(dlconst), rr_dtype(dy.dtype), self.K, self.L, self.M,
@@ -1424,6 +1447,13 @@ def svi_supported_all(F, K, L, M, n_children, dsum, n_ls, table_entries):
     Fourier child's W (Xdim x n) and every centre child's table (Xdim x centres) together."""
     return bool(load_library().rr_glm_svi_supported_all(int(F), int(K), int(L), int(M), int(n_children), int(dsum), int(n_ls),
                                                         int(min(table_entries, 2 ** 31 - 1))))
+
+
+def svi_supported_gm(F, K, L, M, n_children, dsum, n_ls, table_entries):
+    """rr_glm_svi_supported_gm: the range of FusedSvi(..., gm_children=True); table_entries as for svi_supported_all, a
+    spectral-mixture child counting Xdim x n (its dense equivalent V) and 2 Xdim of n_ls."""
+    return bool(load_library().rr_glm_svi_supported_gm(int(F), int(K), int(L), int(M), int(n_children), int(dsum), int(n_ls),
+                                                       int(min(table_entries, 2 ** 31 - 1))))
 
 
 class FeatureMatrix64(object):

@@ -524,9 +524,12 @@ class _ResidentFastFoodGM(_ResidentRFF):
 
     nparams = 2
 
-    def __init__(self, basis, X):
+    def __init__(self, basis, X, dense=False):
         super().__init__(basis, X)  # self.h: the dense handle (n, padded layout of X); self.W = V; self.dT = T+
         self.ff = basis._handles()[0]
+        # dense: the four blocks through the dense handle too (rr_featmat_put_gm: the random Fourier kernels with every frequency
+        # moved by +- mean, what the step-per-call loop does inside) -- block sizes the chain's mixture mode does not serve
+        self.dense = dense
         self.dTm = self.h.dev.zeros(self.W.size * 8)
         self.n = self.h.n
 
@@ -537,10 +540,14 @@ class _ResidentFastFoodGM(_ResidentRFF):
 
     def put(self, fm, X, r0, rows, col0, params):
         self._params(params)
+        if self.dense:
+            return fm.put_gm(self.h, _hip.DeviceView(self.dX, r0, rows), self.mean, self.ls, col0)
         fm.put_fastfood_gm(self.ff, _hip.DeviceView(self.dX, r0, rows), self.mean, self.ls, col0)
 
     def put_batch(self, fm, M, col0, params, slot=None):
         self._params(params)
+        if self.dense:
+            return fm.put_gm(self.h, _hip.DeviceView(_batch_buffer(self, slot), 0, M), self.mean, self.ls, col0)
         fm.put_fastfood_gm(self.ff, _hip.DeviceView(_batch_buffer(self, slot), 0, M), self.mean, self.ls, col0)
 
     def reset(self):
@@ -769,15 +776,18 @@ class MinibatchFeatures(object):
                 c.release()
         self.children = []
 
-    def make_resident(self, X, resident_bases="fourier"):
+    def make_resident(self, X, resident_bases="fourier", dense_gm=False):
         """Keep every child's columns of X on the device for a whole fit (minibatches are then gathered there by
         index); False -- and nothing kept -- if a child cannot.  resident_bases="all" (the estimator's): centre bases of
-        129 .. 4096 input columns are children too."""
+        129 .. 4096 input columns are children too.  dense_gm (the estimator's fused_bases="all+gm"): a FastFoodGM child of
+        Xdim <= 8, whose block size the chain's mixture mode does not serve, is a child through the dense equivalent of its chain."""
         self._drop_children()
         kids = []
         for b in self.bases:
             if resident_bases == "all" and getattr(b, "_child_options", False):
                 c = b._resident_child(X, wide=True)
+            elif dense_gm and getattr(b, "_dense_child_option", False):
+                c = b._resident_child(X, dense_gm=True)
             else:
                 c = b._resident_child(X)
             if c is None:
@@ -1487,9 +1497,17 @@ class FastFoodGM(FastFoodRBF):
     def _chain_fit_ok(self):
         return self.dtype == "f32" and self._handles()[0].gm_chain_ok
 
+    _dense_child_option = True  # `_resident_child` takes dense_gm (the estimator's fused_bases="all+gm", through make_resident)
+
     @slice_transform
-    def _resident_child(self, X, dtype=None):
-        if not self._chain_fit_ok() or dtype == "f64" or X.shape[1] != self.d:
+    def _resident_child(self, X, dtype=None, dense_gm=False):
+        if dtype == "f64" or X.shape[1] != self.d:
+            return None
+        if not self._chain_fit_ok():
+            # block sizes BELOW the chain's mixture mode (d2 < 16, i.e. Xdim <= 8): only for a maker that opted in, and then on
+            # the dense handle alone.  (Block sizes above it -- Xdim > 256 -- are beyond the dense handle's range too: no child.)
+            if dense_gm and self.dtype == "f32" and self._handles()[0].d2 < 16 and self.d <= 8:
+                return _ResidentFastFoodGM(self, X, dense=True)
             return None
         return _ResidentFastFoodGM(self, X)
 

@@ -439,6 +439,7 @@ void rr_basis_destroy(rr_basis *b) {
     if (b->dgfac64) (void)hipFree(b->dgfac64);
     if (b->dmu32) (void)hipFree(b->dmu32);
     if (b->dmu64) (void)hipFree(b->dmu64);
+    if (b->dgm) (void)hipFree(b->dgm);
     if (b->zbuf) (void)hipFree(b->zbuf);
     if (b->lg_xt) (void)hipFree(b->lg_xt);
     if (b->lg_z) (void)hipFree(b->lg_z);

@@ -240,6 +240,48 @@ int rr_featmat_put_rff(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype,
     return fm_put_rff(fm, b, dX, x_dtype, ldx, lenscale, n_ls, col0, false);
 }
 
+}  // extern "C"
+
+struct GmParams {
+    double v[256];
+};
+
+__global__ void __launch_bounds__(256) rr_fm_gm_params_kernel(const GmParams p, int count, double *__restrict__ dst) {
+    if ((int)threadIdx.x < count) dst[threadIdx.x] = p.v[threadIdx.x];
+}
+
+extern "C" {
+
+// A spectral-mixture component through the dense equivalent of its chain: [cos | sin](VX + mX) at col0, [cos | sin](VX - mX) at
+// col0 + 2n -- rr_fm_put_rff_dev twice, as rr_glm_sgd_step does for an RR_SGD_CHILD_GM child (stream order: the second
+// rescaling of W follows the first block's feature kernel).  mean / lenscale (host, d each) go up into the basis' own buffer
+// by a one-block kernel on the stream, behind whatever read it before.
+int rr_featmat_put_gm(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *mean, const double *lenscale,
+                      int64_t col0) {
+    RR_REQUIRE(fm != nullptr && b != nullptr && b->kind == RR_KIND_RFF && mean != nullptr && lenscale != nullptr,
+               "rr_featmat_put_gm: a random Fourier basis (the dense equivalent of the component's chain), mean and lenscale");
+    RR_REQUIRE(b->ctx == fm->ctx, "rr_featmat_put_gm: basis and feature matrix live on different device contexts");
+    RR_REQUIRE(!b->large && b->d <= 128, "rr_featmat_put_gm: needs Xdim <= 128, got %d", b->d);
+    RR_REQUIRE(col0 >= 0 && col0 + 4 * (int64_t)b->n <= fm->F, "rr_featmat_put_gm: columns out of range");
+    const int d = b->d;
+    for (int i = 0; i < d; ++i) {
+        RR_REQUIRE(std::isfinite(mean[i]), "rr_featmat_put_gm: mean[%d] is %g", i, mean[i]);
+        RR_REQUIRE(std::isfinite(lenscale[i]) && lenscale[i] != 0.0, "rr_featmat_put_gm: lenscale[%d] is %g", i, lenscale[i]);
+    }
+    RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
+    if (!b->dgm) RR_CHECK_HIP(hipMalloc((void **)&b->dgm, (size_t)2 * d * sizeof(double)));
+    GmParams par;   // (by value in the kernel's arguments: the caller's arrays are done with when this call returns)
+    for (int i = 0; i < d; ++i) {
+        par.v[i] = mean[i];
+        par.v[d + i] = lenscale[i];
+    }
+    hipLaunchKernelGGL(rr_fm_gm_params_kernel, dim3(1), dim3(256), 0, fm->ctx->stream, par, 2 * d, b->dgm);
+    RR_CHECK_HIP(hipGetLastError());
+    int rc = fm_put_rff(fm, b, dX, x_dtype, ldx, b->dgm + d, d, col0, true, b->dgm, 1.0);
+    if (rc == RR_OK) rc = fm_put_rff(fm, b, dX, x_dtype, ldx, b->dgm + d, d, col0 + 2 * (int64_t)b->n, true, b->dgm, -1.0);
+    return rc;
+}
+
 int rr_featmat_put_linear(rr_featmat *fm, const void *dX, int x_dtype, int64_t ldx, int d, int onescol, int64_t col0) {
     RR_REQUIRE(fm != nullptr && d >= 1 && ldx >= d, "rr_featmat_put_linear: bad argument");
     RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_featmat_put_linear: bad dtype");

@@ -65,6 +65,7 @@ struct rr_basis {
     float *dmu32 = nullptr;       // (dpad,): mean / 2pi of a spectral-mixture component (rr_gm_*)
     double *dmu64 = nullptr;
     double *dgfac64 = nullptr;
+    double *dgm = nullptr;        // (2 d): [mean | length scales] of rr_featmat_put_gm, as given (the device-side rescaling reads them)
     void *zbuf = nullptr;         // feature scratch of the Gram path (f32 or f64), grow-only
     size_t zbuf_bytes = 0;
     std::vector<hipEvent_t> events;  // 5 per row chunk of the last Gram call: features begin / end, SYRK begin / mid / end

@@ -30,7 +30,10 @@
 //
 // Children: random Fourier and linear (rr_glm_svi_create); rr_glm_svi_create_all also takes RadialBasis / SigmoidalBasis
 // (RR_SGD_CHILD_CENTRES: the centres in LDS next to the W tables, features and the length scales' sums in phases c and f,
-// the factor 1 / l^6 or 1 / l^2 once in phase i) and PolynomialBasis (RR_SGD_CHILD_POLY: powers in phase c, no parameters).
+// the factor 1 / l^6 or 1 / l^2 once in phase i) and PolynomialBasis (RR_SGD_CHILD_POLY: powers in phase c, no parameters);
+// rr_glm_svi_create_gm also a spectral-mixture component (RR_SGD_CHILD_GM, basis_functions.py:1386-1562) through the dense
+// equivalent V of its chain: V in LDS like a W table, four trig blocks of (x . V / l +- x . mean) in phase c, 2 d slots
+// [mean | length scales] whose sums are two contractions per slot in phase f.
 //
 // rr_glm_svi_starts evaluates the random starts of structured_sgd (decorators.py:541-583) -- nstarts candidates, each on its
 // own minibatch with its own draws -- as ONE launch, one workgroup per candidate (objective only).
@@ -58,11 +61,14 @@ struct SviChild {
 #define SVI_LS_RFF 0
 #define SVI_LS_RADIAL 1
 #define SVI_LS_SIGMOID 2
+#define SVI_LS_GM_MEAN 3   // a spectral-mixture mean: any sign, never in log space -- a factor, never a divisor
+#define SVI_LS_GM_LS 4     // its length scale: the random Fourier rule
 
 struct SviArgs {
     const SviChild *kid;  // the children's table in device memory (uniform loads; not in the kernel arguments, which would
                           // be copied to registers for the dynamic index)
     int nkids, F, Fp, K, L, M, lik, n_lik, n_ls, ns, updater, y_f64, dsum, wtot;  // wtot: entries of all children's W
+    int ngm;               // RR_SGD_CHILD_GM children (0: nothing of theirs runs)
     int64_t np, N;
     const void *y, *rowarg;
     const double *lconst;  // per row: the f-independent part of loglike (log-factorial terms), or null
@@ -108,16 +114,19 @@ __device__ __forceinline__ double svi_expit(double f) {
 }
 
 // per input dimension, what a child's features multiply x (or x - c) by: 1 / (2 pi l) (random Fourier), 1 / (2 l^2) (radial:
-// X and C are divided by 2 l^2 BEFORE the squared distance, basis_functions.py:685-686), 1 / l (sigmoid, :784)
+// X and C are divided by 2 l^2 BEFORE the squared distance, basis_functions.py:685-686), 1 / l (sigmoid, :784); a
+// spectral-mixture mean multiplies x itself: mean / (2 pi), revolutions like the rest
 __device__ __forceinline__ double svi_ls_scale(int kind, double l) {
+    if (kind == SVI_LS_GM_MEAN) return 0.15915494309189533576888 * l;
     if (kind == SVI_LS_RADIAL) return 1.0 / (2.0 * (l * l));
     if (kind == SVI_LS_SIGMOID) return 1.0 / l;
     return 0.15915494309189533576888 / l;
 }
 
 // the summed contraction of a slot -> its gradient: the factor that depends on l alone, applied ONCE to the K components'
-// sum: 1 / l^2 (random Fourier; sigmoid, basis_functions.py:809-815), 1 / l^6 (radial, :712-719)
+// sum: 1 / l^2 (random Fourier; sigmoid, basis_functions.py:809-815), 1 / l^6 (radial, :712-719), 1 (a spectral-mixture mean)
 __device__ __forceinline__ double svi_ls_grad(int kind, double sm2, double l) {
+    if (kind == SVI_LS_GM_MEAN) return sm2;
     if (kind == SVI_LS_RADIAL) {
         const double l2 = l * l;
         return sm2 / (l2 * l2 * l2);
@@ -281,12 +290,13 @@ __device__ __forceinline__ void svi_gather_issue(const SviArgs &a, const int *id
 }
 
 // launch start: the children's tables into LDS (s.Wl at woff) -- a random Fourier child's W (d, n), a centre child's C^T
-// (d, n) out of the handle's padded float64 copy (row length ldw); they live there for the whole launch
+// (d, n) out of the handle's padded float64 copy (row length ldw), a spectral-mixture child's V (d, n); they live there for the
+// whole launch
 __device__ __forceinline__ void svi_load_tables(const SviArgs &a, const SviLds &s) {
     const int tid = threadIdx.x;
     for (int c = 0; c < a.nkids; ++c) {
         const SviChild &k = a.kid[c];
-        if (k.kind != RR_SGD_CHILD_RFF && k.kind != RR_SGD_CHILD_CENTRES) continue;
+        if (k.kind != RR_SGD_CHILD_RFF && k.kind != RR_SGD_CHILD_CENTRES && k.kind != RR_SGD_CHILD_GM) continue;
         RR_DEV_ASSERT(k.woff >= 0 && k.woff + k.d * k.n <= a.wtot && k.ldw >= k.n);
         for (int o = tid; o < k.d * k.n; o += SVI_THREADS) s.Wl[k.woff + o] = k.W[(size_t)(o / k.n) * k.ldw + o % k.n];
     }
@@ -305,6 +315,20 @@ __device__ __forceinline__ void svi_features(const SviArgs &a, const SviLds &s, 
         s.nb[tid] = g.n;
     }
     svi_sync();
+    if (a.ngm) {
+        // a spectral-mixture child's b = x . mean / (2 pi), ONCE per row: into s.Q (free until pass 2; M nkids <= M F entries)
+        for (int e = tid; e < M * a.nkids; e += SVI_THREADS) {
+            const int c = e / M, r = e % M;
+            const SviChild &k = a.kid[c];
+            if (k.kind != RR_SGD_CHILD_GM) continue;
+            RR_DEV_ASSERT(k.ls0 >= 0 && k.ls0 + 2 * k.d <= a.n_ls && k.xoff + k.d <= a.dsum && e < M * a.F);
+            const ldsd *mu = s.ils + k.ls0;
+            double b = 0.0;
+            for (int i = 0; i < k.d; ++i) b = fma(s.Xb[r * a.dsum + k.xoff + i], mu[i], b);
+            s.Q[e] = b;
+        }
+        svi_sync();
+    }
     for (int c = 0; c < a.nkids; ++c) {
         const SviChild &k = a.kid[c];
         if (k.kind == RR_SGD_CHILD_LINEAR) {
@@ -339,6 +363,26 @@ __device__ __forceinline__ void svi_features(const SviArgs &a, const SviLds &s, 
                     z = fma(t, t, z);
                 }
                 s.Phi[r * a.Fp + k.col0 + j] = k.radial ? exp(-z) : svi_expit(sqrt(z));
+            }
+        } else if (k.kind == RR_SGD_CHILD_GM) {
+            // cos(a + b) | sin(a + b) | cos(a - b) | sin(a - b), each / sqrt(2 n): a = x . V[:, j] / (2 pi l), b per row (above)
+            RR_DEV_ASSERT(k.woff >= 0 && k.woff + k.d * k.n <= a.wtot && k.ls0 >= 0 && k.ls0 + 2 * k.d <= a.n_ls && k.n_ls == 2 * k.d &&
+                          k.col0 + 4 * k.n <= a.F && k.xoff + k.d <= a.dsum);
+            const double scale = 1.0 / sqrt(2.0 * (double)k.n);
+            const ldsd *il = s.ils + k.ls0 + k.d, *V = s.Wl + k.woff;
+            for (int e = tid; e < M * k.n; e += SVI_THREADS) {
+                const int r = e / k.n, j = e % k.n;
+                double t = 0.0;
+                for (int i = 0; i < k.d; ++i) t = fma(s.Xb[r * a.dsum + k.xoff + i], V[i * k.n + j] * il[i], t);
+                const double b = s.Q[c * M + r];
+                ldsd *ph = s.Phi + r * a.Fp + k.col0 + j;
+                double sn, cs;
+                rr_sincos_rev_f64(t + b, sn, cs);
+                ph[0] = cs * scale;
+                ph[k.n] = sn * scale;
+                rr_sincos_rev_f64(t - b, sn, cs);
+                ph[2 * k.n] = cs * scale;
+                ph[3 * k.n] = sn * scale;
             }
         } else {
             const double scale = 1.0 / sqrt((double)k.n);
@@ -694,14 +738,28 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
         for (int h = wave; h < a.n_ls; h += SVI_WAVES) {
             int c = 0;
             while (c + 1 < nk && !(h >= a.kid[c].ls0 && h < a.kid[c].ls0 + a.kid[c].n_ls)) ++c;   // the child that owns slot h
-            RR_DEV_ASSERT(h >= a.kid[c].ls0 && h < a.kid[c].ls0 + a.kid[c].n_ls && a.kid[c].ls0 + a.kid[c].n_ls <= a.n_ls &&
-                          a.kid[c].woff + (h - a.kid[c].ls0 + 1) * a.kid[c].n <= a.wtot);
             const SviChild &kd = a.kid[c];
-            const int i = h - kd.ls0;
+            // (a spectral-mixture child's 2 d slots: means then length scales, both of input dimension i)
+            const bool gm = kd.kind == RR_SGD_CHILD_GM, gm_mean = gm && h - kd.ls0 < kd.d;
+            const int i = gm && !gm_mean ? h - kd.ls0 - kd.d : h - kd.ls0;
+            RR_DEV_ASSERT(h >= kd.ls0 && h < kd.ls0 + kd.n_ls && kd.ls0 + kd.n_ls <= a.n_ls && i >= 0 && i < kd.d &&
+                          kd.woff + (i + 1) * kd.n <= a.wtot);
             const double sc = 1.0 / ((double)L * K);
             const ldsd *W = s.Wl + kd.woff + i * kd.n;
             double acc = 0.0;
-            if (kd.kind == RR_SGD_CHILD_CENTRES) {
+            if (gm) {
+                // t+-[r][j] = x_ri (E_s P_c - E_c P_s) over the + (- : 2 n columns on) block.  mean_i: -(T+ - T-)[i];
+                // l_i: sum_j V_ij (t+ + t-)[r][j], the factor 1 / l_i^2 in phase i -- the + and - blocks in turn
+                RR_DEV_ASSERT(kd.col0 + 4 * kd.n <= a.F && kd.xoff + kd.d <= a.dsum);
+                for (int o = lane; o < 2 * M * kd.n; o += 64) {
+                    const int blk = o / (M * kd.n), q = o % (M * kd.n), r = q / kd.n, j = q % kd.n;
+                    const int jc = kd.col0 + 2 * blk * kd.n + j, js = jc + kd.n;
+                    const double epc = (s.mk[jc] * s.Dr[r] + s.sk[jc] * s.Q[r * F + jc]) * sc;
+                    const double eps = (s.mk[js] * s.Dr[r] + s.sk[js] * s.Q[r * F + js]) * sc;
+                    const double w = gm_mean ? (blk ? 1.0 : -1.0) : W[j];
+                    acc = fma(w * s.Xb[r * a.dsum + kd.xoff + i], eps * s.Phi[r * a.Fp + jc] - epc * s.Phi[r * a.Fp + js], acc);
+                }
+            } else if (kd.kind == RR_SGD_CHILD_CENTRES) {
                 // -sum_{r,j} EdPhi[r][j] dPhi_i[r][j] without the factor of l alone (phase i: 1 / l^6, 1 / l^2):
                 // radial dPhi_i l^6 = Phi (x_i - c_ji)^2; sigmoid dPhi_i l^2 = -|x_i - c_ji| Phi (1 - Phi) -- no division: a row
                 // on a centre gives 0
@@ -963,7 +1021,13 @@ int rr_glm_svi_supported_all(int F, int K, int L, int M, int n_children, int dsu
     return svi_supported(F, K, L, M, n_children, dsum, n_ls, table_entries);
 }
 
-static int svi_create(bool all, const char *who, rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX,
+// (a spectral-mixture child adds no LDS array of its own: V is a table, its 2 d slots are n_ls, its row phases sit in Q)
+int rr_glm_svi_supported_gm(int F, int K, int L, int M, int n_children, int dsum, int n_ls, int table_entries) {
+    return svi_supported(F, K, L, M, n_children, dsum, n_ls, table_entries);
+}
+
+// mode: 0 rr_glm_svi_create, 1 _all (centre and polynomial children too), 2 _gm (and spectral-mixture children)
+static int svi_create(int mode, const char *who, rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX,
                       const int *x_dtype, const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst,
                       int dtype, int K, int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
                       const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_svi **out) {
@@ -984,7 +1048,8 @@ static int svi_create(bool all, const char *who, rr_ctx *ctx, int n_children, co
     o->ctx = ctx;
     SviArgs &a = o->a;
     memset(&a, 0, sizeof a);
-    int col = 0, nls = 0, xoff = 0, woff = 0;
+    const bool all = mode >= 1, gmok = mode == 2;
+    int col = 0, nls = 0, xoff = 0, woff = 0, ngm = 0;
     std::vector<int> lskind;
     for (int s = 0; s < n_children; ++s) {
         const rr_glm_sgd_child &k = children[s];
@@ -998,11 +1063,24 @@ static int svi_create(bool all, const char *who, rr_ctx *ctx, int n_children, co
         c.ldx = ldx[s];
         c.x_f64 = x_dtype[s] == RR_F64;
         bool ok = dX[s] != nullptr && (x_dtype[s] == RR_F32 || x_dtype[s] == RR_F64);
-        if (ok && k.kind == RR_SGD_CHILD_RFF) {
+        const bool gm = gmok && k.kind == RR_SGD_CHILD_GM;
+        if (gm) {
             rr_basis *b = k.basis;
-            ok = b != nullptr && b->kind == RR_KIND_RFF && b->ctx == ctx && (k.n_ls == 1 || k.n_ls == b->d) && (int)b->W.size() == b->d * b->n;
+            if (!(ok && b != nullptr && b->kind == RR_KIND_RFF && b->ctx == ctx && !b->large && b->d <= 128 && k.n_ls == 2 * b->d &&
+                  (int)b->W.size() == b->d * b->n)) {
+                svi_free(o);
+                rr_set_error("%s: child %d: a spectral-mixture child (RR_SGD_CHILD_GM) needs the dense random Fourier equivalent of its "
+                             "chain on this context, Xdim <= 128, n_ls = 2 Xdim coordinates [mean | length scales] (n_ls=%d, Xdim=%d) and "
+                             "its resident rows", who, s, k.n_ls, b != nullptr && b->kind == RR_KIND_RFF ? b->d : -1);
+                return RR_ERR_INVALID;
+            }
+        }
+        if (ok && (k.kind == RR_SGD_CHILD_RFF || gm)) {
+            rr_basis *b = k.basis;
+            ok = gm || (b != nullptr && b->kind == RR_KIND_RFF && b->ctx == ctx && (k.n_ls == 1 || k.n_ls == b->d) && (int)b->W.size() == b->d * b->n);
             if (ok) {
-                c.d = b->d; c.n = b->n; c.n_ls = k.n_ls; c.width = 2 * b->n; c.onescol = 0;
+                c.d = b->d; c.n = b->n; c.n_ls = k.n_ls; c.width = (gm ? 4 : 2) * b->n; c.onescol = 0;
+                ngm += gm ? 1 : 0;
                 double *w = nullptr;
                 if (hipMalloc((void **)&w, b->W.size() * 8) != hipSuccess ||
                     hipMemcpy(w, b->W.data(), b->W.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
@@ -1044,7 +1122,7 @@ static int svi_create(bool all, const char *who, rr_ctx *ctx, int n_children, co
             rr_set_error("%s: child %d: centre and polynomial children (kind %d) are not taken by the fused loop", who, s, k.kind);
             return RR_ERR_INVALID;
         }
-        if (k.kind == RR_SGD_CHILD_GM) {
+        if (k.kind == RR_SGD_CHILD_GM && !gmok) {
             svi_free(o);
             rr_set_error("%s: child %d: a spectral-mixture child (RR_SGD_CHILD_GM) is not taken by the fused loop", who, s);
             return RR_ERR_INVALID;
@@ -1055,12 +1133,14 @@ static int svi_create(bool all, const char *who, rr_ctx *ctx, int n_children, co
                          "linear child with d >= 1 columns, and its resident rows", who, s);
             return RR_ERR_INVALID;
         }
-        for (int h = 0; h < c.n_ls; ++h)
-            lskind.push_back(c.kind == RR_SGD_CHILD_RFF ? SVI_LS_RFF : (c.radial ? SVI_LS_RADIAL : SVI_LS_SIGMOID));
+        for (int h = 0; h < c.n_ls; ++h) {
+            if (c.kind == RR_SGD_CHILD_GM) lskind.push_back(h < c.d ? SVI_LS_GM_MEAN : SVI_LS_GM_LS);
+            else lskind.push_back(c.kind == RR_SGD_CHILD_RFF ? SVI_LS_RFF : (c.radial ? SVI_LS_RADIAL : SVI_LS_SIGMOID));
+        }
         col += c.width;
         nls += c.n_ls;
         xoff += c.d;
-        if (c.kind == RR_SGD_CHILD_RFF || c.kind == RR_SGD_CHILD_CENTRES) {
+        if (c.kind == RR_SGD_CHILD_RFF || c.kind == RR_SGD_CHILD_CENTRES || c.kind == RR_SGD_CHILD_GM) {
             if ((int64_t)woff + (int64_t)c.d * c.n > (1 << 20)) {   // (far beyond one CU's LDS; keeps the offsets in int)
                 svi_free(o);
                 rr_set_error("%s: child %d: the children's tables are outside the fused small-batch loop's range", who, s);
@@ -1072,13 +1152,15 @@ static int svi_create(bool all, const char *who, rr_ctx *ctx, int n_children, co
     a.nkids = n_children; a.F = col; a.Fp = col | 1; a.K = K; a.L = L; a.M = M; a.lik = lik; a.n_lik = n_lik; a.n_ls = nls;
     a.ns = n_children + n_lik + nls; a.updater = updater; a.y_f64 = dtype == RR_F64; a.dsum = xoff; a.N = N; a.wtot = woff;
     a.np = 2 * (int64_t)col * K + a.ns;
+    a.ngm = ngm;
     a.y = dy; a.rowarg = drowarg; a.lconst = dlconst; a.bmag = bmag;
     for (int i = 0; i < 4; ++i) a.up[i] = upd_par[i];
-    if (!(all ? rr_glm_svi_supported_all(a.F, K, L, M, n_children, a.dsum, nls, woff)
-              : rr_glm_svi_supported(a.F, K, L, M, n_children, a.dsum, nls))) {
+    if (!(gmok ? rr_glm_svi_supported_gm(a.F, K, L, M, n_children, a.dsum, nls, woff)
+               : all ? rr_glm_svi_supported_all(a.F, K, L, M, n_children, a.dsum, nls, woff)
+                     : rr_glm_svi_supported(a.F, K, L, M, n_children, a.dsum, nls))) {
         svi_free(o);
         rr_set_error("%s: F = %d, K = %d, nsamples = %d, minibatch = %d is outside the fused small-batch loop's range "
-                     "(rr_glm_svi_supported%s)", who, a.F, K, L, M, all ? "_all" : "");
+                     "(rr_glm_svi_supported%s)", who, a.F, K, L, M, gmok ? "_gm" : (all ? "_all" : ""));
         return RR_ERR_UNSUPPORTED;
     }
     o->lds_bytes = svi_lds_doubles(a) * 8;
@@ -1131,7 +1213,7 @@ int rr_glm_svi_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *child
                       const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K, int L,
                       int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper, const unsigned char *is_log,
                       int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_svi **out) {
-    return svi_create(false, "rr_glm_svi_create", ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dlconst, dtype, K, L, M, lik,
+    return svi_create(0, "rr_glm_svi_create", ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dlconst, dtype, K, L, M, lik,
                       n_lik, z0, lower, upper, is_log, updater, upd_par, maxiter, bmag, out);
 }
 
@@ -1140,7 +1222,16 @@ int rr_glm_svi_create_all(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *c
                           int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
                           const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
                           rr_glm_svi **out) {
-    return svi_create(true, "rr_glm_svi_create_all", ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dlconst, dtype, K, L, M,
+    return svi_create(1, "rr_glm_svi_create_all", ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dlconst, dtype, K, L, M,
+                      lik, n_lik, z0, lower, upper, is_log, updater, upd_par, maxiter, bmag, out);
+}
+
+int rr_glm_svi_create_gm(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                         const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K,
+                         int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
+                         const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
+                         rr_glm_svi **out) {
+    return svi_create(2, "rr_glm_svi_create_gm", ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dlconst, dtype, K, L, M,
                       lik, n_lik, z0, lower, upper, is_log, updater, upd_par, maxiter, bmag, out);
 }
 

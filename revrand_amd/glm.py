@@ -141,13 +141,18 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         kernels walk the dimensions in blocks, and only under "all" are such bases resident at all): their features come from the length
         scales in HBM and their gradient's sums are reduced there.  Such a fit takes the step-per-call loop at every minibatch
         size unless ``fused_bases="all"`` says otherwise.  Any other value: ValueError at ``fit``.
-    fused_bases : "fourier" (default) | "all"
+    fused_bases : "fourier" (default) | "all" | "all+gm"
         Which children the many-steps-per-launch kernel of small minibatches (rr_svi.hip: the reference's default shape, 10
         rows per step) takes.  "fourier": random Fourier, FastFoodRBF and linear children, as before.  "all" (needs
         ``resident_bases="all"``; ValueError at ``fit`` otherwise): RadialBasis, SigmoidalBasis and PolynomialBasis children
         too -- their features and the length scales' gradient are formed inside that kernel in float64 -- whenever the shape
         is in its range (rr_glm_svi_supported_all); a FastFoodGM child, a shape outside the range or several ranks keep the
-        step-per-call loop.  Any other value: ValueError at ``fit``."""
+        step-per-call loop.  "all+gm" (needs ``resident_bases="all"`` too): everything "all" takes plus FastFoodGM children
+        -- a spectral-mixture component through the dense equivalent of its chain (rr_glm_svi_create_gm): four trig blocks
+        per component, 2 Xdim coordinates [mean | length scales] -- whenever the shape is in range (rr_glm_svi_supported_gm).
+        Under this value a FastFoodGM child of Xdim <= 8, which the chain kernel's mixture mode does not serve, stays resident
+        through that dense equivalent (rr_featmat_put_gm), so such a fit has the step-per-call loop as well: out of range,
+        between ranks or with minibatches split over ``devices=``.  Any other value: ValueError at ``fit``."""
 
     def __init__(self, likelihood=Gaussian(), basis=LinearBasis(), K=10, maxiter=3000, batch_size=10, updater=None,
                  nsamples=50, nstarts=500, random_state=None, sampler="host", distributed=False, gram_engine=None,
@@ -192,10 +197,10 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         self._device_predictions()   # (validates predict_engine)
         if getattr(self, "resident_bases", "fourier") not in ("fourier", "all"):
             raise ValueError("resident_bases must be 'fourier' or 'all'")
-        if getattr(self, "fused_bases", "fourier") not in ("fourier", "all"):
-            raise ValueError("fused_bases must be 'fourier' or 'all'")
-        if getattr(self, "fused_bases", "fourier") == "all" and getattr(self, "resident_bases", "fourier") != "all":
-            raise ValueError("fused_bases='all' needs resident_bases='all'")
+        if getattr(self, "fused_bases", "fourier") not in ("fourier", "all", "all+gm"):
+            raise ValueError("fused_bases must be 'fourier', 'all' or 'all+gm'")
+        if getattr(self, "fused_bases", "fourier") in ("all", "all+gm") and getattr(self, "resident_bases", "fourier") != "all":
+            raise ValueError("fused_bases='%s' needs resident_bases='all'" % self.fused_bases)
         self._drop_serving()
         self._dev_seed = None  # the device sampler is re-keyed from random_ per fit
         N, _ = X.shape
@@ -210,7 +215,13 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         # when every basis can keep its columns of X in HBM, minibatches are gathered there: the optimiser then
         # shuffles row INDICES (the same permutation stream) and a zero-width stand-in for X
         every = getattr(self, "resident_bases", "fourier") == "all"   # (the default call is the one it always was)
-        self._resident_fit = self._features().make_resident(X, "all") if every else self._features().make_resident(X)
+        # (fused_bases="all+gm": a FastFoodGM child of Xdim <= 8, which the chain's mixture mode does not serve, stays resident
+        # through the dense equivalent of its chain)
+        gm = every and getattr(self, "fused_bases", "fourier") == "all+gm"
+        if gm:
+            self._resident_fit = self._features().make_resident(X, "all", dense_gm=True)
+        else:
+            self._resident_fit = self._features().make_resident(X, "all") if every else self._features().make_resident(X)
         if self._resident_fit:
             lazy = tuple(_LazyRows(a) if (isinstance(a, np.ndarray) and len(a) == N) else a for a in (y,) + likelihood_args)
             data = (_RowStub(N),) + lazy + (_RowIndex(N),)
@@ -429,20 +440,25 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         kids, n_lik = feats._kids, self._n_lik(params)
         # small minibatches (the reference's default is 10 rows): the whole loop inside one kernel, many steps per launch
         # (not between ranks: that kernel has no exchange step)
-        every = getattr(self, "fused_bases", "fourier") == "all"   # centre and polynomial children in that kernel too
-        taken = ("rff", "linear", "centres", "poly") if every else ("rff", "linear")
+        gm = getattr(self, "fused_bases", "fourier") == "all+gm"   # ... and spectral-mixture components (rr_glm_svi_create_gm)
+        every = gm or getattr(self, "fused_bases", "fourier") == "all"   # centre and polynomial children in that kernel too
+        taken = ("rff", "linear", "centres", "poly") + (("gm",) if gm else ()) if every else ("rff", "linear")
         if self._fused_sgd and os.environ.get("RR_GLM_FUSED", "1") != "0" and y is not None and len(likelihood_args) <= 1 \
                 and np.isfinite(self.maxiter) and comm is None and all(c[0] in taken for c in children):
             N = len(y)
             M = int(min(self.batch_size, N))
             F = int(self.D_)
-            width = {"rff": lambda kid, c: kid.W.shape[0], "centres": lambda kid, c: c[1].d}   # (linear, poly: c[1] columns)
+            width = {"rff": lambda kid, c: kid.W.shape[0], "gm": lambda kid, c: kid.W.shape[0],
+                     "centres": lambda kid, c: c[1].d}   # (linear, poly: c[1] columns)
             dsum = sum(width.get(c[0], lambda kid, c: c[1])(kid, c) for kid, c in zip(kids, children))
-            n_ls = sum(c[2] for c in children if c[0] in ("rff", "centres"))
-            if every:   # the tables the kernel keeps in LDS, counted exactly: W (Xdim, n) and centres (Xdim, M)
-                tables = sum(kid.W.shape[0] * c[1].n if c[0] == "rff" else (c[1].d * c[1].M if c[0] == "centres" else 0)
+            n_ls = sum(c[2] for c in children if c[0] in ("rff", "gm", "centres"))   # (a "gm" child: 2 Xdim [mean | length scales])
+            if every:   # the tables the kernel keeps in LDS, counted exactly: W or V (Xdim, n) and centres (Xdim, M)
+                tables = sum(kid.W.shape[0] * c[1].n if c[0] in ("rff", "gm") else (c[1].d * c[1].M if c[0] == "centres" else 0)
                              for kid, c in zip(kids, children))
-                if _hip.svi_supported_all(F, self.K, self.nsamples, M, len(children), dsum, n_ls, tables):
+                if gm:
+                    if _hip.svi_supported_gm(F, self.K, self.nsamples, M, len(children), dsum, n_ls, tables):
+                        return _FusedLoop(self, feats, n_lik, children, y, likelihood_args, gm_children=True)
+                elif _hip.svi_supported_all(F, self.K, self.nsamples, M, len(children), dsum, n_ls, tables):
                     return _FusedLoop(self, feats, n_lik, children, y, likelihood_args, all_children=True)
             elif _hip.svi_supported(F, self.K, self.nsamples, M, len(children), dsum, n_ls):
                 return _FusedLoop(self, feats, n_lik, children, y, likelihood_args)
@@ -1104,10 +1120,11 @@ class _FusedLoop(object):
     BLOCK_BYTES = 48 << 20    # draws uploaded per launch at most (two device buffers of this size in turn)
     BLOCK_STEPS = 256
 
-    def __init__(self, glm, feats, n_lik, children, y, likelihood_args, all_children=False):
+    def __init__(self, glm, feats, n_lik, children, y, likelihood_args, all_children=False, gm_children=False):
         from . import optimize as opt
         self.glm, self.feats, self.n_lik, self.children = glm, feats, n_lik, children
         self.all_children = all_children   # rr_glm_svi_create_all: centre and polynomial children too
+        self.gm_children = gm_children     # rr_glm_svi_create_gm: and spectral-mixture components
         self.y, self.largs = np.asarray(y, dtype=float), tuple(likelihood_args)
         self.svi = None
         self.updater = opt.Adam() if glm.updater is None else glm.updater
@@ -1145,11 +1162,12 @@ class _FusedLoop(object):
         self.dlc = dev.upload_vector(lc, np.float64) if lc is not None else None
         kids = [c + (kid.dX,) for c, kid in zip(self.children, feats._kids)]
         F = int(g.D_)
-        self.np_ = 2 * F * g.K + len(kids) + self.n_lik + sum(c[2] for c in self.children if c[0] in ("rff", "centres"))
+        self.np_ = 2 * F * g.K + len(kids) + self.n_lik + sum(c[2] for c in self.children if c[0] in ("rff", "gm", "centres"))
         hold = np.zeros(self.np_)
         self.svi = _hip.FusedSvi(dev, kids, len(self.y), self.dy, self.dn, self.dlc, g.K, g.nsamples, self.M, lik, self.n_lik, hold,
                                  np.full(self.np_, -np.inf), np.full(self.np_, np.inf), np.zeros(self.np_, dtype=np.uint8),
-                                 _hip.UPDATER_IDS[kind], par, max(1, int(g.maxiter)), g.B_, all_children=self.all_children)
+                                 _hip.UPDATER_IDS[kind], par, max(1, int(g.maxiter)), g.B_, all_children=self.all_children,
+                                 gm_children=self.gm_children)
         self.F = F
         return self.svi
 
@@ -1232,9 +1250,9 @@ class _FusedLoop(object):
         regs = list(x[o:o + nk])
         ls, q = [], o + nk + self.n_lik
         for c in self.children:
-            n = c[2] if c[0] in ("rff", "centres") else 0   # (a polynomial child's c[2] is its include_bias)
+            n = c[2] if c[0] in ("rff", "gm", "centres") else 0   # (a polynomial child's c[2] is its include_bias)
             if n:
-                ls.append(x[q] if n == 1 else x[q:q + n])
+                ls.append(x[q] if n == 1 else ([x[q:q + n // 2], x[q + n // 2:q + n]] if c[0] == "gm" else x[q:q + n]))
             q += n
         return (regs[0] if nk == 1 else regs), ([x[o + nk]] if self.n_lik else []), (ls[0] if len(ls) == 1 else ls)
 

@@ -398,13 +398,14 @@ class ShardedMinibatchFeatures(object):
         self._parts, self._part_targets = None, {}
 
     # -- which member serves which rows of a minibatch ---------------------------------------------------
-    def make_resident(self, X, resident_bases="fourier"):
+    def make_resident(self, X, resident_bases="fourier", dense_gm=False):
         N = X.shape[0]
         if N < self.n_use * 2:
             return False
         self.bounds = [shard_bounds(N, i, self.n_use) for i in range(self.n_use)]
         self.ends = np.array([e for _, e in self.bounds])
-        ok = self.group.map(lambda i: self.feats[i].make_resident(X[self.bounds[i][0]:self.bounds[i][1]], resident_bases),
+        kw = {"dense_gm": True} if dense_gm else {}
+        ok = self.group.map(lambda i: self.feats[i].make_resident(X[self.bounds[i][0]:self.bounds[i][1]], resident_bases, **kw),
                             members=range(self.n_use))
         if not all(ok):
             self.group.map(lambda i: self.feats[i]._drop_children(), members=range(self.n_use))
