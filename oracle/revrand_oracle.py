@@ -418,7 +418,9 @@ def slm_predict_moments(Phi_s, m, C, var):
 # --------------------------------------------------------------------------
 
 def softplus(f):
-    """mathfun/special.py:91-128: log(1 + exp(f)) through logsumexp([0, f])."""
+    """log(1 + exp(f)) as max(f, 0) + log1p(exp(-|f|)): the exact function to float64 rounding over the whole range (held to 50
+    digits by tests/test_lik_cases_host.py).  Deliberately NOT the reference's form (mathfun/special.py:91-128, a logsumexp of
+    [0, f]), which rounds to 0 below f = -37 and makes log(softplus) -inf there: this is the yardstick, that one is not."""
     f = np.asarray(f, dtype=float)
     return np.maximum(f, 0.) + np.log1p(np.exp(-np.abs(f)))
 

@@ -1137,10 +1137,52 @@ __device__ __forceinline__ float rr_log1p01(float t) {
     const float u = 1.f + t, dd = u - 1.f;
     return dd == 0.f ? t : __logf(u) * __fdividef(t, dd);
 }
-__device__ __forceinline__ float rr_softplus(float f) { return fmaxf(f, 0.f) + rr_log1p01(__expf(-fabsf(f))); }
+// exp(-a) for a >= 0, subnormal results included: the hardware's exp2 returns 0 below 2^-126, so such an argument is raised
+// by 32 and the result scaled back (n exp(f) of a binomial with n = 1000 is 6e-36 at f = -88, not 0)
+__device__ __forceinline__ float rr_expneg(float a) {
+    const float x = -1.44269504088896340736f * a;
+    const bool lo = x < -126.f;
+    return __builtin_amdgcn_exp2f(lo ? x + 32.f : x) * (lo ? 0x1p-32f : 1.f);
+}
+__device__ __forceinline__ float rr_softplus(float f) { return fmaxf(f, 0.f) + rr_log1p01(rr_expneg(fabsf(f))); }
 __device__ __forceinline__ float rr_expit(float f) {
-    const float t = __expf(-fabsf(f));
+    const float t = rr_expneg(fabsf(f));
     return f >= 0.f ? 1.f / (1.f + t) : t / (1.f + t);
+}
+
+// d loglike / d f and the log-likelihood term (Gaussian: the squared error) of one element: the one copy of these formulas,
+// shared by rr_glm_lik_kernel and the epilogue of rr_gemm_lik_f32_kernel.  tests/lik_cases.py holds them to float64 over
+// -200 <= f <= 200 (docs/KERNELS.md, "The likelihood terms over their range").
+template <int LIK>
+__device__ __forceinline__ void rr_lik_elem(float f, float yr, float nn, float ipar, float &df, float &ll) {
+    if (LIK == RR_LIK_BERNOULLI) {
+        df = yr - rr_expit(f);
+        ll = yr * f - rr_softplus(f);
+    } else if (LIK == RR_LIK_BINOMIAL) {
+        df = yr - nn * rr_expit(f);
+        ll = yr * f - nn * rr_softplus(f);
+    } else if (LIK == RR_LIK_GAUSSIAN) {
+        const float er = yr - f;
+        df = er * ipar;
+        ll = er * er;
+    } else if (LIK == RR_LIK_POISSON_EXP) {
+        const float g = __expf(f);
+        df = yr - g;
+        ll = yr * f - g;
+    } else {
+        // Poisson, softplus link: g = softplus(f) = max(f, 0) + t q with t = exp(-|f|) and q = log1p(t) / t in [log 2, 1].
+        // f >= 0: g >= log 2 and the formulas are the plain ones.  f < 0: g = t q underflows (and y / g overflows) long
+        // before the terms do, so expit(f) y / g is formed as y / ((1 + t) q) and log g as f + log q -- no division by g,
+        // nothing to clamp.
+        const bool pos = f >= 0.f;
+        const float t = rr_expneg(fabsf(f)), u = 1.f + t, dd = u - 1.f;
+        const float q = dd == 0.f ? 1.f : __fdividef(__logf(u), dd);  // (u - 1 is exact: log(u) / (u - 1) undoes the rounding of 1 + t)
+        const float g = fmaxf(f, 0.f) + t * q;
+        const float a = (pos ? 1.f : t) / u;  // expit(f)
+        const float b = yr / (pos ? g : u * q);
+        df = pos ? a * (b - 1.f) : b - a;
+        ll = yr * ((pos ? 0.f : f) + __logf(pos ? g : q)) - g;
+    }
 }
 
 template <int LIK, typename TY>
@@ -1154,33 +1196,15 @@ rr_glm_lik_kernel(float *__restrict__ FSt, int64_t M, int64_t rows256, int64_t l
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
     int64_t r1 = r0 + rows_per_block;
     if (r1 > rows256) r1 = rows256;
-    float ll = 0.f, ax = 0.f;
+    float acc = 0.f;  // the log-likelihood terms (Gaussian: the squared errors) of this thread's rows
     const float ipar = LIK == RR_LIK_GAUSSIAN ? 1.f / par : 0.f;
     for (int64_t r = r0; r < r1; ++r) {
         float df = 0.f;
         if (kvalid && r < M) {
-            const float f = FSt[r * ld + kl] * fscale;  // fs was formed with ws / (K L)
-            const float yr = (float)y[r];
-            if (LIK == RR_LIK_BERNOULLI) {
-                df = yr - rr_expit(f);
-                ll += yr * f - rr_softplus(f);
-            } else if (LIK == RR_LIK_BINOMIAL) {
-                const float n = (float)rowarg[r];
-                df = yr - n * rr_expit(f);
-                ll += yr * f - n * rr_softplus(f);
-            } else if (LIK == RR_LIK_GAUSSIAN) {
-                const float e = yr - f;
-                df = e * ipar;
-                ax = fmaf(e, e, ax);
-            } else if (LIK == RR_LIK_POISSON_EXP) {
-                const float g = __expf(f);
-                df = yr - g;
-                ll += yr * f - g;
-            } else {  // Poisson, softplus link
-                const float g = fmaxf(rr_softplus(f), 1e-37f);
-                df = rr_expit(f) * (yr / g - 1.f);
-                ll += yr * __logf(g) - g;
-            }
+            float ll;
+            // fs was formed with ws / (K L)
+            rr_lik_elem<LIK>(FSt[r * ld + kl] * fscale, (float)y[r], LIK == RR_LIK_BINOMIAL ? (float)rowarg[r] : 0.f, ipar, df, ll);
+            acc += ll;
         }
         FSt[r * ld + kl] = df;
     }
@@ -1189,7 +1213,7 @@ rr_glm_lik_kernel(float *__restrict__ FSt, int64_t M, int64_t rows256, int64_t l
     const int k0 = (blockIdx.x * 256) / L;
     for (int i = threadIdx.x; i < 258; i += 256) sacc[i] = 0.f;
     __syncthreads();
-    if (kvalid) atomicAdd(&sacc[kl / L - k0], LIK == RR_LIK_GAUSSIAN ? ax : ll);
+    if (kvalid) atomicAdd(&sacc[kl / L - k0], acc);
     __syncthreads();
     const int klast = blockIdx.x * 256 + 255 < KL ? blockIdx.x * 256 + 255 : KL - 1;
     const int nk = klast >= blockIdx.x * 256 ? klast / L - k0 + 1 : 0;
@@ -1211,30 +1235,6 @@ rr_glm_lik_kernel(float *__restrict__ FSt, int64_t M, int64_t rows256, int64_t l
 // go through LDS to one f64 atomic per component and workgroup.  Saves the likelihood kernel's read + write of fs and
 // the transposing pass over dfs (three passes over rows x kl floats).  Whole K per workgroup (no split-K).
 // ---------------------------------------------------------------------------------------------
-// d loglike / d f and the log-likelihood term of one element (the formulas of rr_glm_lik_kernel)
-template <int LIK>
-__device__ __forceinline__ void rr_lik_elem(float f, float yr, float nn, float ipar, float &df, float &ll) {
-    if (LIK == RR_LIK_BERNOULLI) {
-        df = yr - rr_expit(f);
-        ll = yr * f - rr_softplus(f);
-    } else if (LIK == RR_LIK_BINOMIAL) {
-        df = yr - nn * rr_expit(f);
-        ll = yr * f - nn * rr_softplus(f);
-    } else if (LIK == RR_LIK_GAUSSIAN) {
-        const float er = yr - f;
-        df = er * ipar;
-        ll = er * er;
-    } else if (LIK == RR_LIK_POISSON_EXP) {
-        const float g = __expf(f);
-        df = yr - g;
-        ll = yr * f - g;
-    } else {  // Poisson, softplus link
-        const float g = fmaxf(rr_softplus(f), 1e-37f);
-        df = rr_expit(f) * (yr / g - 1.f);
-        ll = yr * __logf(g) - g;
-    }
-}
-
 struct GemmLikArgs {
     const float *A, *B;   // A = P^T (K = Fp, rows), B = WS^T (Fp, kl)
     float *D, *Dt;        // dfs (rows256, ldd) and dfs^T (kl, ldt); BOTH null: objective only, nothing stored

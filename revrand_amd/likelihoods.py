@@ -14,7 +14,8 @@ RR_LIK_BERNOULLI, RR_LIK_BINOMIAL, RR_LIK_GAUSSIAN, RR_LIK_POISSON_EXP, RR_LIK_P
 
 
 def softplus(f):
-    """log(1 + exp(f)), overflow-safe (mathfun/special.py:91-128)."""
+    """log(1 + exp(f)) as max(f, 0) + log1p(exp(-|f|)): exact to rounding over the whole range.  Deliberately NOT the reference's
+    form (mathfun/special.py:91-128, a logsumexp of [0, f]), which rounds to 0 below f = -37 -- log(softplus) is then -inf."""
     f = np.asarray(f, dtype=float)
     return np.maximum(f, 0.) + np.log1p(np.exp(-np.abs(f)))
 
