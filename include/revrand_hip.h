@@ -242,6 +242,10 @@ int rr_featmat_gram(rr_featmat *fm, const void *dy, int y_dtype, double *dG, dou
 /* The rows of the current rr_featmat_begin as they sit in HBM, padding columns included: out host float32 (rows, ld) with
  * ld = F rounded up to a multiple of 256.  For tests and diagnostics (what a put_* call wrote, and what it left alone). */
 int rr_featmat_download(rr_featmat *fm, float *out);
+/* The feature-major copy P^T next to P, once a transposing pass has laid it out for the current row count (else
+ * RR_ERR_INVALID): out host float32 (F, max_rows rounded up to a multiple of 256).  For tests and diagnostics: the blocks a
+ * random Fourier child writes there while it writes P. */
+int rr_featmat_download_pt(rr_featmat *fm, float *out);
 
 /* ---- bases defined by centres: RadialBasis, SigmoidalBasis (basis_functions.py:616-815); PolynomialBasis (:496-576) ----
  * With x_n a row of X, c_j row j of the centres C (M, d) and l the length scale -- one for every dimension (n_ls == 1) or

@@ -97,6 +97,7 @@ SIGNATURES = {
     "rr_featmat_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p]),
     "rr_featmat_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "rr_featmat_download_pt": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "rr_centres_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_void_p, _c_void_pp]),
     "rr_centres_transform": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
@@ -991,6 +992,13 @@ class FeatureMatrix(object):
         """The rows of the last `begin` as they sit in HBM, (rows, ld) float32 with the padding columns (rr_featmat_download)."""
         out = np.empty((self.rows, (self.F + 255) // 256 * 256), dtype=np.float32)
         _check(self.lib, self.lib.rr_featmat_download(self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def download_pt(self):
+        """P^T as it sits next to P, (F, max_rows rounded up to 256) float32, once a transposing pass has laid it out for the
+        current row count (rr_featmat_download_pt)."""
+        out = np.empty((self.F, (self.max_rows + 255) // 256 * 256), dtype=np.float32)
+        _check(self.lib, self.lib.rr_featmat_download_pt(self.h, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
     def put_centres(self, handle, dX, lenscale, col0):

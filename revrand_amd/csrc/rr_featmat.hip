@@ -361,6 +361,16 @@ int rr_featmat_download(rr_featmat *fm, float *out) {
     return RR_OK;
 }
 
+int rr_featmat_download_pt(rr_featmat *fm, float *out) {
+    RR_REQUIRE(fm != nullptr && out != nullptr, "rr_featmat_download_pt: null argument");
+    float *Pt = rr_fm_pass2_pt(fm->pass2);
+    RR_REQUIRE(Pt != nullptr && fm->pt_rows == fm->rows, "rr_featmat_download_pt: no P^T is laid out for this row count");
+    RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
+    RR_CHECK_HIP(hipMemcpyAsync(out, Pt, (size_t)fm->F * fm->max_rows * sizeof(float), hipMemcpyDeviceToHost, fm->ctx->stream));
+    RR_CHECK_HIP(hipStreamSynchronize(fm->ctx->stream));
+    return RR_OK;
+}
+
 // y^T y into *dyty: atomics, or (deterministic mode) per-block partials added in order
 static int fm_yty(rr_ctx *c, const void *dy, int y_dtype, int64_t rows, double *dyty) {
     int yb = (int)((rows + 255) / 256);

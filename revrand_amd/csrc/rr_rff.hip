@@ -575,7 +575,10 @@ static bool rr_features_mfma_launch(rr_basis *b, const TX *X, const TX *y, int64
 // loads; any pairing of the k index works as long as A and B agree).  Per tile and column block KS MFMAs give the
 // phases of 16 x 16 (row, frequency) pairs, lane (j, g) owning frequency c0 + j and rows r0 + g + 4 e; the VALU is left
 // with the float64 sin / cos kernels only, and every store instruction writes 4 rows x 128 contiguous bytes.
-template <int DMAX, int CB, bool HAS_Y, typename TX, typename TO>
+// F32TRIG (float output only): RR_F32P64's float32 hardware sine / cosine of the float64 phase.  Without it a float output is
+// float64 arithmetic throughout, rounded once at the store -- what rr_rff_transform_kernel gives the remaining rows of a
+// float64 transform with float32 output.
+template <int DMAX, int CB, bool HAS_Y, typename TX, typename TO, bool F32TRIG = false>
 __global__ void __launch_bounds__(256)
 rr_rff_features_mfma64_kernel(const TX *__restrict__ X, const TX *__restrict__ y, int64_t N, int64_t Npad, int64_t ldx,
                               const double *__restrict__ Ws, int n, int npad, TO *__restrict__ P, int64_t ldp,
@@ -654,6 +657,17 @@ rr_rff_features_mfma64_kernel(const TX *__restrict__ X, const TX *__restrict__ y
                             bc[cb] = fma(cv, yv[e], bc[cb]);
                             bs[cb] = fma(sv, yv[e], bs[cb]);
                         }
+                    } else if constexpr (!F32TRIG) {
+                        double sv, cv;
+                        rr_sincos_rev_f64(acc[e], sv, cv);
+                        const float cf = rr < lim ? (float)(cv * scale) : 0.f;
+                        const float sf = rr < lim ? (float)(sv * scale) : 0.f;
+                        asm volatile("global_store_dword %0, %1, %2 offset:%3" RR_NT_ASM ::"v"(off), "v"(cf), "s"(tile_c), "i"(64 * cb) : "memory");
+                        asm volatile("global_store_dword %0, %1, %2 offset:%3" RR_NT_ASM ::"v"(off), "v"(sf), "s"(tile_s), "i"(64 * cb) : "memory");
+                        if (HAS_Y) {
+                            bc[cb] = fma((double)cf, yv[e], bc[cb]);
+                            bs[cb] = fma((double)sf, yv[e], bs[cb]);
+                        }
                     } else {
                         // RR_F32P64: the float64 phase loses its whole revolutions in float64 (exact), what is left in
                         // [-0.5, 0.5] goes through the float32 hardware sin / cos like every f32 feature (2^-24 revolutions)
@@ -693,7 +707,7 @@ rr_rff_features_mfma64_kernel(const TX *__restrict__ X, const TX *__restrict__ y
 
 // launch (A'') when its preconditions hold (x rows aligned for the lanes' vector loads); false = use the VALU kernel.
 // The output must have whole 16-row tiles.
-template <typename TX, typename TO>
+template <typename TX, typename TO, bool F32TRIG = false>
 static bool rr_features_mfma64_launch(rr_basis *b, const TX *X, const TX *y, int64_t m, int64_t mpad, int64_t ldx, TO *P,
                                       int64_t ldp, double *db, double scale) {
     static const bool disabled = getenv("RR_FEATURES_NO_MFMA64") != nullptr;
@@ -712,12 +726,12 @@ static bool rr_features_mfma64_launch(rr_basis *b, const TX *X, const TX *y, int
             void *part = nullptr;                                                                                   \
             const int64_t nslots = (int64_t)grid.y * 4, F2 = 2 * (int64_t)b->n;                                     \
             if (rr_det_scratch(c, (size_t)nslots * F2 * 8, &part) != RR_OK) return false;                           \
-            hipLaunchKernelGGL((rr_rff_features_mfma64_kernel<DM, CBK, true, TX, TO>), grid, dim3(256), 0, c->stream, \
+            hipLaunchKernelGGL((rr_rff_features_mfma64_kernel<DM, CBK, true, TX, TO, F32TRIG>), grid, dim3(256), 0, c->stream, \
                                X, y, m, mpad, ldx, b->dWs64, b->n, b->npad, P, ldp, (double *)part, scale, (int)tpb, F2); \
             if (rr_det_reduce(c, (const double *)part, nslots, F2, F2, db) != RR_OK) return false;                  \
-        } else if (y) hipLaunchKernelGGL((rr_rff_features_mfma64_kernel<DM, CBK, true, TX, TO>), grid, dim3(256), 0, c->stream, \
+        } else if (y) hipLaunchKernelGGL((rr_rff_features_mfma64_kernel<DM, CBK, true, TX, TO, F32TRIG>), grid, dim3(256), 0, c->stream, \
                                   X, y, m, mpad, ldx, b->dWs64, b->n, b->npad, P, ldp, db, scale, (int)tpb);        \
-        else hipLaunchKernelGGL((rr_rff_features_mfma64_kernel<DM, CBK, false, TX, TO>), grid, dim3(256), 0, c->stream, \
+        else hipLaunchKernelGGL((rr_rff_features_mfma64_kernel<DM, CBK, false, TX, TO, F32TRIG>), grid, dim3(256), 0, c->stream, \
                                 X, y, m, mpad, ldx, b->dWs64, b->n, b->npad, P, ldp, db, scale, (int)tpb);          \
     } while (0)
     switch (b->dpad) {
@@ -2961,7 +2975,7 @@ static int launch_gram(rr_basis *b, const void *dX, const void *dy, int64_t N, i
         if (done_a) {
         } else if (F32 && b->phase64) {
             if constexpr (F32)
-                done_a = rr_features_mfma64_launch<TX, float>(b, Xc, yc, m, mpad, ldx, (float *)P, ldp, db, 1.0 / sqrt((double)b->n));
+                done_a = rr_features_mfma64_launch<TX, float, true>(b, Xc, yc, m, mpad, ldx, (float *)P, ldp, db, 1.0 / sqrt((double)b->n));
             if (!done_a) {
                 rr_set_error("gram: a float64-phase basis (RR_F32P64) needs 16-byte aligned rows of X");
                 return RR_ERR_UNSUPPORTED;
@@ -3045,8 +3059,8 @@ int rr_features_rowmajor_f32(rr_basis *b, const void *dX, int x_dtype, int64_t m
     if (b->phase64) {  // RR_F32P64: phases on the f64 matrix cores, float32 features out; no direct P^T (consumers transpose)
         const double sc = scale_mult / sqrt((double)b->n);
         const bool done = x_dtype == RR_F32
-                              ? rr_features_mfma64_launch<float, float>(b, (const float *)dX, nullptr, m, mpad, ldx, P, ldp, nullptr, sc)
-                              : rr_features_mfma64_launch<double, float>(b, (const double *)dX, nullptr, m, mpad, ldx, P, ldp, nullptr, sc);
+                              ? rr_features_mfma64_launch<float, float, true>(b, (const float *)dX, nullptr, m, mpad, ldx, P, ldp, nullptr, sc)
+                              : rr_features_mfma64_launch<double, float, true>(b, (const double *)dX, nullptr, m, mpad, ldx, P, ldp, nullptr, sc);
         if (!done) {
             rr_set_error("features: a float64-phase basis (RR_F32P64) needs 16-byte aligned rows of X");
             return RR_ERR_UNSUPPORTED;

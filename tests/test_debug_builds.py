@@ -379,3 +379,51 @@ def test_bounds_build_counts_the_fastfood_instance_each_case_runs():
     reachable = E.reachable_idents()
     assert not bad, bad
     assert set(ran) == reachable, (sorted(reachable - set(ran)), sorted(set(ran) - reachable))
+
+
+def _rff_variants():
+    import rff_cases as R
+    return [None] + list(R.SWITCHES)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("switch", _rff_variants(), ids=lambda s: s or "default")
+def test_bounds_build_counts_the_feature_kernel_each_route_takes(switch):
+    """One call per census case of tests/test_gpu_rff_exact.py under the bounds-checking build, which counts launches per
+    kernel: the matrix-core, VALU, large-Xdim (transpose, GEMM with and without the cos / sin epilogue, float64 phase, trig),
+    gradient, spectral-mixture and rescaling kernels ran as often as `feature_route` of tests/rff_cases.py predicts for this
+    device's CU count and no other of them ran -- by default, and once per switch read at process start (RR_FEATURES_NO_MFMA,
+    RR_FEATURES_NO_MFMA64: no launch of the kernel switched off; RR_PREPARE_ON_HOST: no rescaling kernel).  Every counted call
+    also met its per-element bound and left the sentinel around its block.  The counter drops template arguments: DMAX, the
+    (x, out) type pairs and HAS_Y / WT are not told apart here -- tests/test_rff_cases_host.py's coverage test and the results
+    hold them.  The children share the Gram module's guard: none is started after one that failed, reported a bounds
+    violation or hung."""
+    if not os.path.exists(DEBUG_LIB):
+        pytest.skip("make -C revrand_amd/csrc debug has not been run")
+    import test_gpu_gram_exact as E
+    import test_gpu_rff_exact as X
+    env = {"REVRAND_HIP_LIB": DEBUG_LIB}
+    if switch:
+        env[switch] = "1"
+    rows = E.guarded_child("the feature-kernel census under %s" % (switch or "the default switches"),
+                           X.CHILD_CODE + "print('CENSUS', json.dumps(X.census(%r)))\n" % (switch,), env, "CENSUS", timeout=900,
+                           forbidden=("RR_BOUNDS",))
+    bad, ran = [], set()
+    for label, cu, got, want, wrong in rows:
+        print("%-44s cu=%d %s" % (label, cu, " ".join("%s=%d" % (k.replace("rr_", "").replace("_kernel", ""), v)
+                                                      for k, v in sorted((got or {}).items()) if v)))
+        ran |= {k for k, v in (got or {}).items() if v}
+        if got != want or wrong:
+            bad.append((label, {k: (got[k], want[k]) for k in want if got is None or got[k] != want[k]} if got else None, wrong))
+    assert len(rows) >= (300 if switch is None else 4) and not bad, bad[:10]
+    if switch is None:
+        assert {"rr_rff_features_mfma_kernel", "rr_rff_features_mfma64_kernel", "rr_rff_transform_kernel", "rr_rff_grad_kernel",
+                "rr_rff_features_kernel", "rr_rff_grad_p_kernel", "rr_xt_kernel", "rr_gemm_trig_f32_kernel", "rr_gemm_tn_small_f32_kernel",
+                "rr_phase_f64_kernel", "rr_trig_kernel", "rr_scale_w_kernel", "rr_scale_w_dev_kernel", "rr_gm_transform_kernel",
+                "rr_gm_grad_kernel"} <= ran, sorted(ran)
+    elif switch == "RR_FEATURES_NO_MFMA":
+        assert "rr_rff_features_mfma_kernel" not in ran and "rr_rff_features_kernel" in ran
+    elif switch == "RR_FEATURES_NO_MFMA64":
+        assert "rr_rff_features_mfma64_kernel" not in ran and "rr_rff_features_kernel" in ran
+    else:
+        assert "rr_scale_w_kernel" not in ran
