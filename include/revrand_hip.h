@@ -692,6 +692,15 @@ int rr_featmat_predict_begin_b(rr_featmat *fm, const double *m, const float *dB,
  * rr_fastfood_vx on the identity) through the rr_rff_* entry points -- the chain is linear in x. */
 int rr_fastfood_create(rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B, const double *G,
                        const int64_t *PI, const double *S, rr_basis **out);
+/* rr_fastfood_create serves block sizes d2 <= 256 (d <= 256 input columns) and refuses larger ones.  WIDE blocks,
+ * 512 <= d2 <= 4096 (256 < d <= 4096), come from this entry point: same arguments, same handle kind, served by
+ * rr_fastfood_transform[_dev], rr_fastfood_vx and rr_featmat_put_fastfood in both arithmetics (one wave per row and block,
+ * a 4096-point transform in registers; docs/KERNELS.md 3.43).  d2 > 4096 is RR_ERR_INVALID with a message naming 4096,
+ * d2 <= 256 is RR_ERR_INVALID pointing at rr_fastfood_create.  The mixture-component entry points
+ * (rr_fastfood_gm_transform[_dev], rr_featmat_put_fastfood_gm) refuse a wide handle with RR_ERR_UNSUPPORTED: FastFoodGM
+ * keeps 16 <= d2 <= 256. */
+int rr_fastfood_create_wide(rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B, const double *G,
+                            const int64_t *PI, const double *S, rr_basis **out);
 
 /* Phi = [cos VX, sin VX] / sqrt(n), (N, 2n): FastFoodRBF.transform (basis_functions.py:1263-1289)
  * by the Hadamard / permute / diagonal chain (in-wave butterflies, LDS permutation gather). */

@@ -250,6 +250,9 @@ SIGNATURES = {
     "rr_fastfood_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           _c_void_pp]),
+    "rr_fastfood_create_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               _c_void_pp]),
     "rr_fastfood_transform": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                              ctypes.c_int, ctypes.c_int64]),
@@ -1575,10 +1578,15 @@ def hadamard(Y, ordering=True, device=None):
     return out
 
 
-class FastFoodHandle(object):
-    """Device-resident FastFood block matrices (rr_basis of kind FASTFOOD)."""
+FASTFOOD_MAX_DIM = 4096    # rr_fastfood_create_wide: the largest block size (and input width) of the FastFoodRBF chain
 
-    def __init__(self, d, d2, k, B, G, PI, S, compute="f32", device=None):
+
+class FastFoodHandle(object):
+    """Device-resident FastFood block matrices (rr_basis of kind FASTFOOD).  ``wide``: the caller's basis class serves block
+    sizes above 256 (FastFoodRBF; up to FASTFOOD_MAX_DIM) -- such a handle comes from rr_fastfood_create_wide.  Without it,
+    and at d2 <= 256 either way, rr_fastfood_create decides (and refuses d2 > 256)."""
+
+    def __init__(self, d, d2, k, B, G, PI, S, compute="f32", device=None, wide=False):
         self.dev = get_device(device)
         self.lib = self.dev.lib
         self.d, self.d2, self.k, self.n = d, d2, k, d2 * k
@@ -1589,11 +1597,10 @@ class FastFoodHandle(object):
         if not (B.shape == G.shape == PI.shape == S.shape == (k, d2)):
             raise ValueError("FastFood matrices must all have shape (k, d2)")
         h = ctypes.c_void_p()
-        _check(self.lib, self.lib.rr_fastfood_create(self.dev.ctx, {"f32": RR_F32, "f64": RR_F64}[compute], d, d2, k,
-                                                     B.ctypes.data_as(ctypes.c_void_p),
-                                                     G.ctypes.data_as(ctypes.c_void_p),
-                                                     PI.ctypes.data_as(ctypes.c_void_p),
-                                                     S.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h)))
+        create = self.lib.rr_fastfood_create_wide if wide and d2 > 256 else self.lib.rr_fastfood_create
+        _check(self.lib, create(self.dev.ctx, {"f32": RR_F32, "f64": RR_F64}[compute], d, d2, k,
+                                B.ctypes.data_as(ctypes.c_void_p), G.ctypes.data_as(ctypes.c_void_p),
+                                PI.ctypes.data_as(ctypes.c_void_p), S.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h)))
         self.h = h
 
     def __del__(self):

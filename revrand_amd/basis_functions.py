@@ -1322,6 +1322,9 @@ class FastFoodRBF(_LengthScaleBasis):
         super(_LengthScaleBasis, self).__init__(regularizer)
 
     def _init_dims(self, nbases, Xdim):
+        if self._wide_chain and Xdim > _hip.FASTFOOD_MAX_DIM:
+            raise ValueError("{}: Xdim={} exceeds the chain kernels' largest block size, {}".format(
+                type(self).__name__, Xdim, _hip.FASTFOOD_MAX_DIM))
         l = int(np.ceil(np.log2(Xdim)))
         self.nbases = nbases
         self.d = Xdim
@@ -1361,7 +1364,8 @@ class FastFoodRBF(_LengthScaleBasis):
         cache, key = _handle_cache(self)
         h = cache.get(key)
         if h is None:
-            ff = _hip.FastFoodHandle(self.d, self.d2, self.k, self.B, self.G, self.PI, self.S, compute=self.dtype)
+            ff = _hip.FastFoodHandle(self.d, self.d2, self.k, self.B, self.G, self.PI, self.S, compute=self.dtype,
+                                     wide=type(self)._wide_chain)
             h = cache[key] = (ff, FastFoodRBF._LazyDense(self, ff))
         return h
 
@@ -1420,10 +1424,12 @@ class FastFoodRBF(_LengthScaleBasis):
         return _ResidentFastFood(self, X)
 
     _resident_via_chain = True
+    _wide_chain = True  # block sizes 512 .. 4096 (256 < Xdim <= 4096) by rr_fastfood_create_wide; FastFoodGM: up to 256 only
 
     @slice_transform
     def device_fit_state(self, X, y):
-        """(X, y) resident for a whole fit.  f32: the statistics pass runs the CHAIN (rr_fastfood16_kernel -> feature matrix
+        """(X, y) resident for a whole fit.  f32: the statistics pass runs the CHAIN (rr_fastfood16_kernel, or
+        rr_fastfood64_kernel at Xdim > 256 -> feature matrix
         -> MFMA SYRK) and the second pass contracts X^T A against the same features -- a one-child CatFitState.  f64 (or
         RR_FASTFOOD_FIT=dense, A/B runs): the dense equivalent W through the random Fourier kernels."""
         if X.shape[1] != self.d:
@@ -1470,6 +1476,8 @@ class FastFoodGM(FastFoodRBF):
             return Parameter(np.ones(self.d) * param.value, param.bounds)
         raise ValueError("Parameter dimension doesn't agree with X dimensions!")
 
+    _wide_chain = False  # the chain's mixture mode (and the handle it runs on) ends at d2 = 256
+
     def get_dim(self, X):
         return 4 * self.n
 
@@ -1505,7 +1513,7 @@ class FastFoodGM(FastFoodRBF):
             return None
         if not self._chain_fit_ok():
             # block sizes BELOW the chain's mixture mode (d2 < 16, i.e. Xdim <= 8): only for a maker that opted in, and then on
-            # the dense handle alone.  (Block sizes above it -- Xdim > 256 -- are beyond the dense handle's range too: no child.)
+            # the dense handle alone.  (Block sizes above it -- Xdim > 256 -- have no FastFoodGM handle at all: no child.)
             if dense_gm and self.dtype == "f32" and self._handles()[0].d2 < 16 and self.d <= 8:
                 return _ResidentFastFoodGM(self, X, dense=True)
             return None

@@ -17,25 +17,29 @@
 #include "rr_internal.h"
 
 // A chain-kernel launch.  The bounds-checking build counts it under an identifier that names the instance --
-// family/R<registers>/<vx|phi|gm>, and for the lane-major families /<vec|scalar>/<full|partial> -- because the launch
+// family/R<registers>/<vx|phi|gm>, for the lane-major families /<vec|scalar>/<full|partial>, for the wide family
+// /<vec|scalar> -- because the launch
 // macro's own spelling of a kernel held in a variable is just that variable's name (rr_debug_kernel_launches; no '<', '('
 // or blank, so the identifier is kept whole).  The release build is the plain launch.
 #ifdef RR_BOUNDS
 #include <string>
 static std::string ff_instance_id(const char *family, int R, bool phi, bool gm, int vec, int full) {
     std::string id = std::string(family) + "/R" + std::to_string(R) + (gm ? "/gm" : phi ? "/phi" : "/vx");
-    if (vec >= 0) id += std::string(vec ? "/vec" : "/scalar") + (full ? "/full" : "/partial");
+    if (vec >= 0) id += vec ? "/vec" : "/scalar";
+    if (vec >= 0 && full >= 0) id += full ? "/full" : "/partial";  // (the wide family has no partial waves: full < 0)
     return id;
 }
-#define RR_FF_LAUNCH(family, R, phi, gm, vec, full, kern, grid, stream, ...)                                   \
+#define RR_FF_LAUNCH_T(threads, family, R, phi, gm, vec, full, kern, grid, stream, ...)                        \
     do {                                                                                                        \
         rr_launch_device_check((stream), __FILE__, __LINE__, ff_instance_id(family, R, phi, gm, vec, full).c_str()); \
-        hipLaunchKernelGGLInternal((kern), (grid), dim3(256), 0, (stream), __VA_ARGS__);                        \
+        hipLaunchKernelGGLInternal((kern), (grid), dim3(threads), 0, (stream), __VA_ARGS__);                    \
     } while (0)
 #else
-#define RR_FF_LAUNCH(family, R, phi, gm, vec, full, kern, grid, stream, ...) \
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, __VA_ARGS__)
+#define RR_FF_LAUNCH_T(threads, family, R, phi, gm, vec, full, kern, grid, stream, ...) \
+    hipLaunchKernelGGL(kern, grid, dim3(threads), 0, stream, __VA_ARGS__)
 #endif
+// (workgroups of 256 threads, except the wide family's float64 instance at d2 = 4096)
+#define RR_FF_LAUNCH(...) RR_FF_LAUNCH_T(256, __VA_ARGS__)
 
 template <typename TC>
 __device__ __forceinline__ void ff_sincos_rev(TC t, TC &s, TC &c);
@@ -685,6 +689,184 @@ rr_fastfood16d_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, i
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Wide blocks, d2 = 64 R with R in {8, 16, 32, 64} (512 .. 4096; FastFoodRBF on 256 < Xdim <= 4096), both arithmetics.
+// ONE WAVE owns one (row, block) transform: element(lane, q) = (q / VW) * 64 VW + lane * VW + q % VW with VW = 16 bytes of
+// the compute type, so a lane's table loads, its LDS line writes and its stores are 16-byte vectors and the 64 lanes of a
+// group cover 1 KiB contiguous.  The WHT is separable over index bits: the log2(R) register bits are register butterflies
+// (packed f32), lane bits 0-3 the DPP butterflies of the 16-lane kernels (row_fwht / row_fwht64), lane bits 4 and 5 the
+// half-row / half-wave swaps of xor_partner (float64: __shfl_xor) -- a 4096-point transform with no LDS and no barrier.  The
+// permutation gather goes through a per-wave LDS line of d2 elements (wave-synchronous, as above).
+// The waves of a workgroup share block j = blockIdx.x and deal the rows of the workgroup's chunk among themselves.  The four
+// diagonals and PI are 4 R registers: held for the whole chunk at R <= 16 (TAB), read per row from the L2-resident tables at
+// R = 32, 64 (all waves of a workgroup, and every workgroup of the block, read the same 4 d2 entries).  Workgroups are 4
+// waves except at d2 = 4096 in float64, where two 32 KiB lines fill the 64 KiB of static LDS.
+// ---------------------------------------------------------------------------------------------
+template <typename TC>
+constexpr int ff64_waves(int R) { return 64 * R * (int)sizeof(TC) * 4 <= 65536 ? 4 : 2; }
+
+template <int R, bool PHI, bool VEC, typename TX, typename TC, typename TO>
+__global__ void __launch_bounds__(ff64_waves<TC>(R) * 64)
+rr_fastfood64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, int k, const TC *__restrict__ Bm,
+                     const TC *__restrict__ Gm, const int *__restrict__ PIm, const TC *__restrict__ Sm,
+                     const TC *__restrict__ invls, TO *__restrict__ out, int64_t ldo, TC scale, int rows_per_block) {
+    constexpr int D2 = 64 * R;
+    constexpr int VW = 16 / (int)sizeof(TC);   // contiguous elements per lane and group
+    constexpr int NG = R / VW;                 // groups of 64 VW elements
+    constexpr int WPB = ff64_waves<TC>(R);
+    constexpr bool TAB = R <= 16;              // the tables of the block live in registers
+    constexpr bool F32 = sizeof(TC) == 4;
+    typedef TX xvec __attribute__((ext_vector_type(VW)));
+    typedef TO ovec __attribute__((ext_vector_type(VW)));
+    typedef TC cvec __attribute__((ext_vector_type(VW)));
+    typedef int ivec __attribute__((ext_vector_type(VW)));
+    __shared__ __attribute__((aligned(16))) TC perm[WPB][D2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = blockIdx.x;
+    const int n = D2 * k;
+    const int lo = lane * VW;                  // element of register 0; register q: (q / VW) * 64 VW + lo + q % VW
+    // x rows hold d <= d2 elements; an output row holds n (VX) or 2 n (Phi) columns; one workgroup column per block
+    RR_DEV_ASSERT(d >= 1 && d <= D2 && d <= ldx && (PHI ? 2 : 1) * (int64_t)n <= ldo && j < k && (int)blockDim.x == WPB * 64 &&
+                  (!VEC || (d % VW == 0 && ldx % VW == 0 && ldo % VW == 0)));
+
+    // Group g of this lane's share of a table: one 16-byte load (8 bytes of PI next to float64 values).  Without TAB the
+    // lane's offset `to` is made opaque once per row (below): the loads of a row then depend on a value defined inside the
+    // row loop and stay there -- hoisted out of it as loop invariants they would be 4 R live registers again
+    int to = lo;
+    const TC *Bb = Bm + (size_t)j * D2, *Gb = Gm + (size_t)j * D2, *Sb = Sm + (size_t)j * D2;
+    const int *Pb = PIm + (size_t)j * D2;
+    auto ld_c = [&](const TC *base, int g) { return *reinterpret_cast<const cvec *>(base + to + g * 64 * VW); };
+    auto ld_p = [&](int g) {
+        const ivec t = *reinterpret_cast<const ivec *>(Pb + to + g * 64 * VW);
+#pragma unroll
+        for (int w = 0; w < VW; ++w) RR_DEV_ASSERT(t[w] >= 0 && t[w] < D2);
+        return t;
+    };
+    // L = B / l (the +-1 diagonal folded into 1 / l: d2 entries of 1 / l, zero beyond d), G, S = S d2^-1.5 (/ 2 pi when PHI:
+    // the phase in revolutions) and PI
+    cvec Lv[TAB ? NG : 1], Gv[TAB ? NG : 1], Sv[TAB ? NG : 1];
+    ivec Pv[TAB ? NG : 1];
+    if constexpr (TAB) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            Lv[g] = ld_c(invls, g) * ld_c(Bb, g);
+            Gv[g] = ld_c(Gb, g);
+            Sv[g] = ld_c(Sb, g);
+            Pv[g] = ld_p(g);
+        }
+    }
+    auto tab_L = [&](int g) { return TAB ? Lv[TAB ? g : 0] : ld_c(invls, g) * ld_c(Bb, g); };
+    auto tab_G = [&](int g) { return TAB ? Gv[TAB ? g : 0] : ld_c(Gb, g); };
+    auto tab_S = [&](int g) { return TAB ? Sv[TAB ? g : 0] : ld_c(Sb, g); };
+    auto tab_P = [&](int g) { return TAB ? Pv[TAB ? g : 0] : ld_p(g); };
+    TC sg[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) sg[b] = (lane >> b) & 1 ? TC(-1) : TC(1);
+    TC *line = perm[wave];
+
+    int64_t r = (int64_t)blockIdx.y * rows_per_block;
+    int64_t r1 = r + rows_per_block;
+    if (r1 > N) r1 = N;
+    r += wave;
+    if (r >= r1) return;  // (no barriers in this kernel)
+    // x of this wave's next row is fetched while the current one is transformed (AHEAD), where x and v together stay within
+    // 128 registers; the largest instances (float64 x at d2 = 4096, float64 arithmetic at d2 = 4096) load x where they use
+    // it and leave the latency to the other waves of the SIMD.  Elements >= d are read from a clamped address of the same
+    // row and meet 1 / l = 0 (as in rr_fastfood16_kernel: a non-finite x makes the whole row non-finite either way, as in
+    // the reference)
+    constexpr bool AHEAD = R * (sizeof(TX) + sizeof(TC)) <= 512;
+    auto load_xg = [&](int64_t row, int g) {
+        const TX *xr = X + row * ldx;
+        const int e = g * 64 * VW + lo;
+        xvec t;
+        if (VEC) {
+            t = *reinterpret_cast<const xvec *>(xr + (e < d ? e : 0));  // d % VW == 0: a group is in or out
+        } else {
+#pragma unroll
+            for (int w = 0; w < VW; ++w) t[w] = xr[e + w < d ? e + w : 0];
+        }
+        return t;
+    };
+    auto fwht = [&](TC (&v)[R]) {
+        if constexpr (F32) row_fwht<R>(v, sg);
+        else row_fwht64<R>(v, sg);
+        fwht_stage<16, R, TC>(v, lane);
+        fwht_stage<32, R, TC>(v, lane);
+    };
+    xvec xn[AHEAD ? NG : 1];
+    if constexpr (AHEAD) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) xn[g] = load_xg(r, g);
+    }
+    for (; r < r1; r += WPB) {
+        if constexpr (!TAB) asm volatile("" : "+v"(to));
+        TC v[R];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const cvec l = tab_L(g);
+            const xvec x = AHEAD ? xn[AHEAD ? g : 0] : load_xg(r, g);
+#pragma unroll
+            for (int w = 0; w < VW; ++w) v[g * VW + w] = (TC)x[w] * l[w];
+        }
+        if constexpr (AHEAD) {
+            const int64_t rn = r + WPB < r1 ? r + WPB : r;
+#pragma unroll
+            for (int g = 0; g < NG; ++g) xn[g] = load_xg(rn, g);
+        }
+        fwht(v);
+        // the permutation, through the wave's LDS line (64 lanes x 16 B contiguous per group on the way in, single words on
+        // the way out).  Same wave wrote and reads: LDS operations of a wave execute in order
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            cvec t;
+#pragma unroll
+            for (int w = 0; w < VW; ++w) t[w] = v[g * VW + w];
+            *reinterpret_cast<cvec *>(line + g * 64 * VW + lo) = t;
+        }
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const ivec p = tab_P(g);
+            const cvec gg = tab_G(g);
+#pragma unroll
+            for (int w = 0; w < VW; ++w) v[g * VW + w] = line[p[w]] * gg[w];
+        }
+        fwht(v);
+        // a group of a lane is VW contiguous outputs, the 64 lanes 1 KiB (f32 out) contiguous: non-temporal vector stores
+        // straight from the registers, group by group
+        TO *orow = out + r * ldo + (int64_t)j * D2 + lo;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const cvec ss = tab_S(g);
+            TO o0[VW], o1[VW];
+#pragma unroll
+            for (int w = 0; w < VW; ++w) {
+                const TC ph = v[g * VW + w] * ss[w];
+                if constexpr (PHI) {
+                    TC s, c;
+                    ff_sincos_rev<TC>(ph, s, c);
+                    o0[w] = (TO)(c * scale);
+                    o1[w] = (TO)(s * scale);
+                } else {
+                    o0[w] = (TO)ph;
+                }
+            }
+            auto store = [&](TO *o, const TO (&src)[VW]) {
+                if (VEC) {
+                    ovec t;
+#pragma unroll
+                    for (int w = 0; w < VW; ++w) t[w] = src[w];
+                    __builtin_nontemporal_store(t, reinterpret_cast<ovec *>(o));
+                } else {
+#pragma unroll
+                    for (int w = 0; w < VW; ++w) __builtin_nontemporal_store(src[w], &o[w]);
+                }
+            };
+            store(orow + g * 64 * VW, o0);
+            if constexpr (PHI) store(orow + n + g * 64 * VW, o1);
+        }
+    }
+}
+
 // mathfun.linalg.hadamard: rows x n (n = 2^p <= 4096), natural order, normalised by 1/n; optional
 // sequency reordering (linalg.py:223-236).  One workgroup per row, butterflies in LDS.
 template <typename TC>
@@ -722,19 +904,24 @@ rr_hadamard_kernel(const TC *__restrict__ Y, int64_t rows, int n, int ordering, 
 // ---------------------------------------------------------------------------------------------
 static size_t ff_dtype_size(int t) { return t == RR_F32 ? 4 : 8; }
 
+// Rows per workgroup of the lane-major and the wide families: whole rounds of equal-cost workgroups -- `occ` of this instance
+// fit a CU (its registers decide: 5 at d2 = 128), `cols` workgroup columns share the row blocks of a round -- so that the grid is
+// m x (CUs x occ) with at most 512 rows each; at least 4 rows, at most 65535 row blocks.  `env`: RR_FF_ROWS_PER_BLOCK overrides
+// (measurement and tests; read at every call)
+static int64_t ff_rows_per_wg(const rr_ctx *c, int64_t N, int occ, int64_t cols, bool env) {
+    const int64_t per = std::max<int64_t>(1, (int64_t)c->num_cu * occ / cols);  // row blocks per round
+    const int64_t m = std::max<int64_t>(1, (N + per * 512 - 1) / (per * 512));
+    int64_t rp = (N + per * m - 1) / (per * m);
+    if (rp < 4) rp = 4;
+    if (env && getenv("RR_FF_ROWS_PER_BLOCK")) rp = std::max(1, atoi(getenv("RR_FF_ROWS_PER_BLOCK")));
+    if ((N + rp - 1) / rp > 65535) rp = (N + 65534) / 65535;
+    return rp;
+}
+
 template <bool PHI, typename TX, typename TC, typename TO, bool GM = false>
 static int ff_launch(rr_basis *b, const void *dX, int64_t N, int64_t ldx, void *dOut, int64_t ldo) {
     rr_ctx *c = b->ctx;
     const int d2 = b->ff_d2, k = b->ff_k;
-    const int lane_len = d2 < 64 ? d2 : 64;
-    const int bpw = 64 / lane_len;
-    const int R = d2 <= 64 ? 1 : d2 / 64;
-    const unsigned gx = (unsigned)((k + 4 * bpw - 1) / (4 * bpw));
-    int64_t rpb = (N * gx + (int64_t)c->num_cu * 8 - 1) / ((int64_t)c->num_cu * 8);
-    if (rpb < 8) rpb = 8;
-    if (rpb > 512) rpb = 512;
-    if ((N + rpb - 1) / rpb > 65535) rpb = (N + 65534) / 65535;
-    const dim3 grid(gx, (unsigned)((N + rpb - 1) / rpb));
     const bool f32 = sizeof(TC) == 4;
     const TC *Bm = (const TC *)(f32 ? (void *)b->ffB32 : (void *)b->ffB64);
     const TC *Gm = (const TC *)(f32 ? (void *)b->ffG32 : (void *)b->ffG64);
@@ -746,6 +933,40 @@ static int ff_launch(rr_basis *b, const void *dX, int64_t N, int64_t ldx, void *
         rr_set_error("fastfood: the mixture-component chain kernel serves 16 <= d2 <= 256 (d2 = %d: use the dense route)", d2);
         return RR_ERR_UNSUPPORTED;
     }
+    if constexpr (!GM) {
+        if (d2 >= 512) {  // wide blocks (rr_fastfood_create_wide handles): one wave per (row, block)
+            constexpr int vw = 16 / (int)sizeof(TC);
+            // the same conditions as the 16-lane families: rows, row widths and both pointers fit vw-element vectors
+            const bool vec = (ldx % vw == 0) && (ldo % vw == 0) && (b->d % vw == 0) && ((uintptr_t)dX % (vw * sizeof(TX)) == 0) &&
+                             ((uintptr_t)dOut % (vw * sizeof(TO)) == 0) && !getenv("RR_FF_NO_VEC");
+#define RR_FF64_(RR, VEC)                                                                                            \
+    do {                                                                                                             \
+        auto kern = rr_fastfood64_kernel<RR, PHI, VEC, TX, TC, TO>;                                                  \
+        constexpr int threads = ff64_waves<TC>(RR) * 64;                                                             \
+        static int occ = 0;                                                                                          \
+        if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, 0) != hipSuccess || occ < 1)) occ = 2; \
+        const int64_t rp = ff_rows_per_wg(c, N, occ, k, true);                                                       \
+        RR_FF_LAUNCH_T(threads, "rr_fastfood64_kernel", RR, PHI, false, VEC, -1, kern,                               \
+                       dim3((unsigned)k, (unsigned)((N + rp - 1) / rp)), c->stream, (const TX *)dX, N, ldx, b->d, k, Bm, Gm,  \
+                       b->ffPI, Sm, Lm, (TO *)dOut, ldo, scale, (int)rp);                                            \
+    } while (0)
+#define RR_FF64(RR)                    \
+    do {                               \
+        if (vec) RR_FF64_(RR, true);   \
+        else RR_FF64_(RR, false);      \
+    } while (0)
+            switch (d2 / 64) {  // (rr_fastfood_create_wide admits 512, 1024, 2048 and 4096)
+                case 8: RR_FF64(8); break;
+                case 16: RR_FF64(16); break;
+                case 32: RR_FF64(32); break;
+                default: RR_FF64(64); break;
+            }
+#undef RR_FF64
+#undef RR_FF64_
+            RR_CHECK_HIP(hipGetLastError());
+            return RR_OK;
+        }
+    }
     if constexpr (sizeof(TC) == 8) {  // float64 arithmetic: the lane-major kernel with float64 registers
         static const bool old_kernel64 = getenv("RR_FASTFOOD_OLD") != nullptr;
         if ((GM || !old_kernel64) && d2 >= 16 && d2 <= 256) {
@@ -754,20 +975,12 @@ static int ff_launch(rr_basis *b, const void *dX, int64_t N, int64_t ldx, void *
             const bool vec = (ldx % vw == 0) && (ldo % vw == 0) && (b->d % vw == 0) && ((uintptr_t)dX % (vw * sizeof(TX)) == 0) &&
                              ((uintptr_t)dOut % (vw * sizeof(TO)) == 0) && !getenv("RR_FF_NO_VEC");
             const bool full = (k % 4 == 0);
-            auto rows_per_wg = [&](int occ) {  // whole rounds of equal-cost workgroups, at most 512 rows each
-                const int64_t per = std::max<int64_t>(1, (int64_t)c->num_cu * occ / gx16);
-                const int64_t m = std::max<int64_t>(1, (N + per * 512 - 1) / (per * 512));
-                int64_t rp = (N + per * m - 1) / (per * m);
-                if (rp < 4) rp = 4;
-                if ((N + rp - 1) / rp > 65535) rp = (N + 65534) / 65535;
-                return rp;
-            };
 #define RR_FF16D_(RR, VEC, FULL)                                                                                     \
     do {                                                                                                             \
         auto kern = rr_fastfood16d_kernel<RR, PHI, VEC, FULL, TX, TO, GM>;                                           \
         static int occ = 0;                                                                                          \
         if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, 0) != hipSuccess || occ < 1)) occ = 2; \
-        const int64_t rp = rows_per_wg(occ);                                                                         \
+        const int64_t rp = ff_rows_per_wg(c, N, occ, gx16, false);                                                   \
         RR_FF_LAUNCH("rr_fastfood16d_kernel", RR, PHI, GM, VEC, FULL, kern, dim3(gx16, (unsigned)((N + rp - 1) / rp)),   \
                      c->stream, (const TX *)dX, N, ldx, b->d, k, (const double *)Bm, (const double *)Gm, b->ffPI,    \
                      (const double *)Sm, (const double *)Lm, (TO *)dOut, ldo, (double)scale, (int)rp,                \
@@ -801,23 +1014,12 @@ static int ff_launch(rr_basis *b, const void *dX, int64_t N, int64_t ldx, void *
             const bool vec = (ldx % vw == 0) && (ldo % vw == 0) && (b->d % vw == 0) && ((uintptr_t)dX % (vw * sizeof(TX)) == 0) &&
                              ((uintptr_t)dOut % (vw * sizeof(TO)) == 0) && !getenv("RR_FF_NO_VEC");
             const bool full = (k % 4 == 0);
-            // whole rounds of equal-cost workgroups: occ of this instance fit a CU (its registers decide: 5 at d2 = 128);
-            // rows per workgroup so that the grid is m x (CUs x occ) with at most 512 rows each
-            auto rows_per_wg = [&](int occ) {
-                const int64_t per = std::max<int64_t>(1, (int64_t)c->num_cu * occ / gx16);  // row blocks per round
-                const int64_t m = std::max<int64_t>(1, (N + per * 512 - 1) / (per * 512));
-                int64_t rp = (N + per * m - 1) / (per * m);
-                if (rp < 4) rp = 4;
-                if (getenv("RR_FF_ROWS_PER_BLOCK")) rp = std::max(1, atoi(getenv("RR_FF_ROWS_PER_BLOCK")));  // measurement only
-                if ((N + rp - 1) / rp > 65535) rp = (N + 65534) / 65535;
-                return rp;
-            };
 #define RR_FF16_(RR, VEC, FULL)                                                                                      \
     do {                                                                                                             \
         auto kern = rr_fastfood16_kernel<RR, PHI, VEC, FULL, TX, TO, GM>;                                            \
         static int occ = 0;                                                                                          \
         if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, 0) != hipSuccess || occ < 1)) occ = 4; \
-        const int64_t rp = rows_per_wg(occ);                                                                         \
+        const int64_t rp = ff_rows_per_wg(c, N, occ, gx16, true);                                                    \
         RR_FF_LAUNCH("rr_fastfood16_kernel", RR, PHI, GM, VEC, FULL, kern, dim3(gx16, (unsigned)((N + rp - 1) / rp)),    \
                      c->stream, (const TX *)dX, N, ldx, b->d, k, (const float *)Bm, (const float *)Gm, b->ffPI,      \
                      (const float *)Sm, (const float *)Lm, (TO *)dOut, ldo, (float)scale, (int)rp, (const float *)Mm); \
@@ -841,6 +1043,16 @@ static int ff_launch(rr_basis *b, const void *dX, int64_t N, int64_t ldx, void *
             return RR_OK;
         }
     }
+    // the lane-minor kernel: d2 < 16, and 16 <= d2 <= 256 under RR_FASTFOOD_OLD
+    const int lane_len = d2 < 64 ? d2 : 64;
+    const int bpw = 64 / lane_len;
+    const int R = d2 <= 64 ? 1 : d2 / 64;
+    const unsigned gx = (unsigned)((k + 4 * bpw - 1) / (4 * bpw));
+    int64_t rpb = (N * gx + (int64_t)c->num_cu * 8 - 1) / ((int64_t)c->num_cu * 8);
+    if (rpb < 8) rpb = 8;
+    if (rpb > 512) rpb = 512;
+    if ((N + rpb - 1) / rpb > 65535) rpb = (N + 65534) / 65535;
+    const dim3 grid(gx, (unsigned)((N + rpb - 1) / rpb));
 #define RR_FF(RR)                                                                                                  \
     RR_FF_LAUNCH("rr_fastfood_kernel", RR, PHI, false, -1, -1, (rr_fastfood_kernel<RR, PHI, TX, TC, TO>), grid, c->stream, \
                  (const TX *)dX, N, ldx, b->d, d2, k, Bm, Gm, b->ffPI, Sm, Lm, (TO *)dOut, ldo, scale, (int)rpb)
@@ -964,17 +1176,23 @@ static int ff_host_call(rr_basis *b, const void *X, int x_dtype, int64_t N, int6
     return rc;
 }
 
-extern "C" {
-
-int rr_fastfood_create(rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B, const double *G,
-                       const int64_t *PI, const double *S, rr_basis **out) {
-    RR_REQUIRE(ctx != nullptr && out != nullptr && B && G && PI && S, "rr_fastfood_create: null argument");
+// rr_fastfood_create (d2 <= 256: the lane-major and lane-minor kernels, the mixture mode) and rr_fastfood_create_wide
+// (512 <= d2 <= 4096: rr_fastfood64_kernel, FastFoodRBF only) differ in the range they accept and in nothing else
+static int ff_create(const char *who, bool wide, rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B,
+                     const double *G, const int64_t *PI, const double *S, rr_basis **out) {
+    RR_REQUIRE(ctx != nullptr && out != nullptr && B && G && PI && S, "%s: null argument", who);
     *out = nullptr;
-    RR_REQUIRE(d >= 1 && k >= 1 && d2 >= d && (d2 & (d2 - 1)) == 0, "rr_fastfood_create: need d2 = 2^p >= d, k >= 1");
-    RR_REQUIRE(d2 <= 256, "rr_fastfood_create: d2=%d > 256 is not supported yet", d2);
-    RR_REQUIRE(compute == RR_F32 || compute == RR_F64, "rr_fastfood_create: bad compute dtype %d", compute);
+    RR_REQUIRE(d >= 1 && k >= 1 && d2 >= d && (d2 & (d2 - 1)) == 0, "%s: need d2 = 2^p >= d, k >= 1", who);
+    if (wide) {
+        RR_REQUIRE(d2 <= 4096, "%s: d2=%d > 4096 is not supported", who, d2);
+        RR_REQUIRE(d2 > 256, "%s: d2=%d <= 256 is served by rr_fastfood_create", who, d2);
+        RR_REQUIRE((int64_t)d2 * k <= INT32_MAX / 2, "%s: 2 d2 k = %lld columns exceed the int32 range", who, 2LL * d2 * k);
+    } else {
+        RR_REQUIRE(d2 <= 256, "%s: d2=%d > 256 is not supported yet", who, d2);
+    }
+    RR_REQUIRE(compute == RR_F32 || compute == RR_F64, "%s: bad compute dtype %d", who, compute);
     for (size_t i = 0; i < (size_t)k * d2; ++i)
-        RR_REQUIRE(PI[i] >= 0 && PI[i] < d2 && (B[i] == 1 || B[i] == -1), "rr_fastfood_create: bad B/PI entry at %zu", i);
+        RR_REQUIRE(PI[i] >= 0 && PI[i] < d2 && (B[i] == 1 || B[i] == -1), "%s: bad B/PI entry at %zu", who, i);
     RR_CHECK_HIP(hipSetDevice(ctx->device));
     const size_t cnt = (size_t)k * d2;
     const double norm = pow((double)d2, -1.5);  // (1/d2)(1/d2) sqrt(d2): both WHT normalisations and :1368
@@ -1011,12 +1229,24 @@ int rr_fastfood_create(rr_ctx *ctx, int compute, int d, int d2, int k, const int
     if (e == hipSuccess) e = hipMalloc((void **)&b->ffL64, (size_t)d2 * 8);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        rr_set_error("rr_fastfood_create: device allocation failed: %s", hipGetErrorString(e));
+        rr_set_error("%s: device allocation failed: %s", who, hipGetErrorString(e));
         rr_basis_destroy(b);
         return RR_ERR_OOM;
     }
     *out = b;
     return RR_OK;
+}
+
+extern "C" {
+
+int rr_fastfood_create(rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B, const double *G,
+                       const int64_t *PI, const double *S, rr_basis **out) {
+    return ff_create("rr_fastfood_create", false, ctx, compute, d, d2, k, B, G, PI, S, out);
+}
+
+int rr_fastfood_create_wide(rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B, const double *G,
+                            const int64_t *PI, const double *S, rr_basis **out) {
+    return ff_create("rr_fastfood_create_wide", true, ctx, compute, d, d2, k, B, G, PI, S, out);
 }
 
 int rr_fastfood_transform(rr_basis *b, const void *X, int x_dtype, int64_t N, int64_t ldx, const double *lenscale,
