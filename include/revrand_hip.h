@@ -701,6 +701,13 @@ int rr_fastfood_create(rr_ctx *ctx, int compute, int d, int d2, int k, const int
  * keeps 16 <= d2 <= 256. */
 int rr_fastfood_create_wide(rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B, const double *G,
                             const int64_t *PI, const double *S, rr_basis **out);
+/* WIDE blocks for FastFoodGM (FastFoodGM(..., wide_chain=True) on 256 < d <= 4096): the arguments, range and refusals of
+ * rr_fastfood_create_wide.  Such a handle serves everything a wide handle serves (rr_fastfood_vx builds V = _makeVX(I_d))
+ * and, in addition, the mixture-component entry points below -- rr_fastfood_gm_transform[_dev] and
+ * rr_featmat_put_fastfood_gm, (N, 4 d2 k) features -- by the mixture mode of the wide kernel (docs/KERNELS.md 3.44).
+ * 4 d2 k must fit the int32 range.  Handles of the two entry points above behave as before. */
+int rr_fastfood_create_wide_gm(rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B, const double *G,
+                               const int64_t *PI, const double *S, rr_basis **out);
 
 /* Phi = [cos VX, sin VX] / sqrt(n), (N, 2n): FastFoodRBF.transform (basis_functions.py:1263-1289)
  * by the Hadamard / permute / diagonal chain (in-wave butterflies, LDS permutation gather). */
@@ -726,7 +733,8 @@ int rr_gm_grad(rr_basis *basis, const void *X, int x_dtype, int64_t N, int64_t l
                const double *lenscale, int n_ls, void *dmean, void *dlen, int out_dtype);
 
 /* The same features by the Hadamard / permute / diagonal CHAIN itself, on an rr_fastfood_create handle (16 <= d2 <= 256;
- * RR_ERR_UNSUPPORTED otherwise -- the dense route above serves those):  VX from the chain kernel, mX = x . mean reduced in
+ * RR_ERR_UNSUPPORTED otherwise -- the dense route above serves those) or an rr_fastfood_create_wide_gm handle
+ * (512 <= d2 <= 4096): VX from the chain kernel, mX = x . mean reduced in
  * registers next to it, four trig blocks of width n = d2 k scaled by 1 / sqrt(2 n) -- no dense (d, n) equivalent, no
  * (N, n) intermediate.  Host buffers (N, 4n) / device buffers / straight into a device feature matrix at columns
  * [col0, col0 + 4n), where the block pairs [cos | sin](VX + mX) at col0 and [cos | sin](VX - mX) at col0 + 2n look like

@@ -253,6 +253,9 @@ SIGNATURES = {
     "rr_fastfood_create_wide": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                _c_void_pp]),
+    "rr_fastfood_create_wide_gm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  _c_void_pp]),
     "rr_fastfood_transform": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                              ctypes.c_int, ctypes.c_int64]),
@@ -1584,7 +1587,9 @@ FASTFOOD_MAX_DIM = 4096    # rr_fastfood_create_wide: the largest block size (an
 class FastFoodHandle(object):
     """Device-resident FastFood block matrices (rr_basis of kind FASTFOOD).  ``wide``: the caller's basis class serves block
     sizes above 256 (FastFoodRBF; up to FASTFOOD_MAX_DIM) -- such a handle comes from rr_fastfood_create_wide.  Without it,
-    and at d2 <= 256 either way, rr_fastfood_create decides (and refuses d2 > 256)."""
+    and at d2 <= 256 either way, rr_fastfood_create decides (and refuses d2 > 256).  ``wide="gm"`` (FastFoodGM under
+    wide_chain=True): at d2 > 256 the handle comes from rr_fastfood_create_wide_gm -- a wide handle that serves the
+    mixture-component entry points too."""
 
     def __init__(self, d, d2, k, B, G, PI, S, compute="f32", device=None, wide=False):
         self.dev = get_device(device)
@@ -1597,7 +1602,9 @@ class FastFoodHandle(object):
         if not (B.shape == G.shape == PI.shape == S.shape == (k, d2)):
             raise ValueError("FastFood matrices must all have shape (k, d2)")
         h = ctypes.c_void_p()
-        create = self.lib.rr_fastfood_create_wide if wide and d2 > 256 else self.lib.rr_fastfood_create
+        self.wide_gm = isinstance(wide, str) and wide == "gm" and d2 > 256
+        create = self.lib.rr_fastfood_create_wide_gm if self.wide_gm else (
+            self.lib.rr_fastfood_create_wide if wide and d2 > 256 else self.lib.rr_fastfood_create)
         _check(self.lib, create(self.dev.ctx, {"f32": RR_F32, "f64": RR_F64}[compute], d, d2, k,
                                 B.ctypes.data_as(ctypes.c_void_p), G.ctypes.data_as(ctypes.c_void_p),
                                 PI.ctypes.data_as(ctypes.c_void_p), S.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h)))
@@ -1643,8 +1650,9 @@ class FastFoodHandle(object):
 
     @property
     def gm_chain_ok(self):
-        """The chain kernels' mixture-component mode serves this block size (16 <= d2 <= 256)."""
-        return 16 <= self.d2 <= 256
+        """The chain kernels' mixture-component mode serves this handle: block sizes 16 <= d2 <= 256, and the wide blocks
+        (512 <= d2 <= 4096) of a ``wide="gm"`` handle."""
+        return self.wide_gm or 16 <= self.d2 <= 256
 
     def gm_transform(self, X, mean, lenscale, out_dtype=np.float64):
         """FastFoodGM.transform by the chain kernel: (N, 4n) = [cos | sin](VX + mX), [cos | sin](VX - mX), / sqrt(2n)."""

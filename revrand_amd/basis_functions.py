@@ -1450,14 +1450,27 @@ class FastFoodGM(FastFoodRBF):
     Parameters are always (d,)-shaped ``mean`` and ``lenscale`` (scalars are broadcast, :1539-1549);
     ``grad`` returns the pair (dPhi/dmean, dPhi/dlenscale).  Runs on the dense equivalent of the
     FastFood chain (``rr_gm_transform`` / ``rr_gm_grad``).
+
+    ``wide_chain=True`` opts in to inputs of 256 < Xdim <= 4096 columns (without it such a basis has no device route and
+    ``transform`` raises; Xdim <= 256 behaves the same either way, Xdim > 4096 raises ``ValueError`` at construction): the
+    handle then comes from ``rr_fastfood_create_wide_gm`` and the mixture mode of the wide chain kernel serves ``transform``
+    (both arithmetics), ``gram``, ``predict_moments``, ``device_fit_state`` (resident ``StandardLinearModel`` fits, alone or
+    as a child of a concatenation) and the step-per-call minibatch loop of ``GeneralizedLinearModel``.  Unchanged by the
+    keyword: the materialised ``grad`` (two (N, 4n, d) tensors) is refused above 128 columns by the dense route, the
+    estimator's resident and fused SVI loops take children of at most 128 columns, and deterministic mode keeps its
+    Xdim <= 128 limit.
     """
 
     @slice_init
     def __init__(self, nbases, Xdim, mean=Parameter(norm_dist(), Bound()), lenscale=Parameter(gamma(1.), Positive()),
-                 regularizer=None, random_state=None, dtype="f32"):
+                 regularizer=None, random_state=None, dtype="f32", wide_chain=False):
         if dtype not in ("f32", "f64"):
             raise ValueError("dtype must be 'f32' or 'f64'")
         self.dtype = dtype
+        self.wide_chain = bool(wide_chain)
+        if self.wide_chain and Xdim > _hip.FASTFOOD_MAX_DIM:
+            raise ValueError("{}: Xdim={} exceeds the chain kernels' largest block size, {}".format(
+                type(self).__name__, Xdim, _hip.FASTFOOD_MAX_DIM))
         self.random_state = random_state  # for repr
         self._random = check_random_state(random_state)
         self._init_dims(nbases, Xdim)
@@ -1476,7 +1489,19 @@ class FastFoodGM(FastFoodRBF):
             return Parameter(np.ones(self.d) * param.value, param.bounds)
         raise ValueError("Parameter dimension doesn't agree with X dimensions!")
 
-    _wide_chain = False  # the chain's mixture mode (and the handle it runs on) ends at d2 = 256
+    # the chain's mixture mode (and the handle it runs on) ends at d2 = 256 by default; an instance built with
+    # wide_chain=True asks for the wide mixture handle instead (`_handles`)
+    _wide_chain = False
+    wide_chain = False  # (instances unpickled from before the keyword)
+
+    def _handles(self):
+        cache, key = _handle_cache(self)
+        h = cache.get(key)
+        if h is None:
+            ff = _hip.FastFoodHandle(self.d, self.d2, self.k, self.B, self.G, self.PI, self.S, compute=self.dtype,
+                                     wide="gm" if self.wide_chain else False)
+            h = cache[key] = (ff, FastFoodRBF._LazyDense(self, ff))
+        return h
 
     def get_dim(self, X):
         return 4 * self.n
@@ -1485,7 +1510,7 @@ class FastFoodGM(FastFoodRBF):
     def transform(self, X, mean=None, lenscale=None):
         """(N, 4*n) float64 (basis_functions.py:1443-1475): the chain kernel's mixture mode (VX by the Hadamard / permute /
         diagonal chain, mX = X . mean next to it in registers); block sizes it does not serve (d2 < 16, i.e. Xdim <= 8) go
-        through the dense equivalent of the chain."""
+        through the dense equivalent of the chain.  Xdim > 256 needs ``wide_chain=True`` (the wide kernel's mixture mode)."""
         mean = self._check_dim(X.shape[1], mean, paramind=0)
         lenscale = self._check_dim(X.shape[1], lenscale, paramind=1)
         ff, dense = self._handles()
@@ -1513,7 +1538,7 @@ class FastFoodGM(FastFoodRBF):
             return None
         if not self._chain_fit_ok():
             # block sizes BELOW the chain's mixture mode (d2 < 16, i.e. Xdim <= 8): only for a maker that opted in, and then on
-            # the dense handle alone.  (Block sizes above it -- Xdim > 256 -- have no FastFoodGM handle at all: no child.)
+            # the dense handle alone.  (Block sizes above it -- Xdim > 256 without wide_chain=True -- have no FastFoodGM handle at all: no child.)
             if dense_gm and self.dtype == "f32" and self._handles()[0].d2 < 16 and self.d <= 8:
                 return _ResidentFastFoodGM(self, X, dense=True)
             return None
@@ -1533,7 +1558,9 @@ class FastFoodGM(FastFoodRBF):
         lenscale = self._check_dim(X.shape[1], lenscale, paramind=1)
         ff, dense = self._handles()
         if not ff.gm_chain_ok or self.dtype != "f32":
-            return fm.put_host(dense.gm_transform(X, mean, lenscale), col0)
+            # (a wide mixture handle: the dense route ends at 128 columns, the chain's host call serves float64 too)
+            gm_transform = ff.gm_transform if ff.wide_gm else dense.gm_transform
+            return fm.put_host(gm_transform(X, mean, lenscale), col0)
         dX = fm.dev.upload_matrix(np.ascontiguousarray(X, dtype=np.float32))
         fm.put_fastfood_gm(ff, dX, mean, lenscale, col0)
         fm.dev.sync()
@@ -1553,9 +1580,9 @@ class FastFoodGM(FastFoodRBF):
         return BasisCat._of([self]).predict_moments(X, hypers, m, C)
 
     def __repr__(self):
-        return "{}(nbases={}, Xdim={}, mean={}, lenscale={}, regularizer={}, random_state={})".format(
+        return "{}(nbases={}, Xdim={}, mean={}, lenscale={}, regularizer={}, random_state={}{})".format(
             type(self).__name__, self.nbases, self.d, self.params[0], self.params[1], self.regularizer,
-            self.random_state)
+            self.random_state, ", wide_chain=True" if self.wide_chain else "")
 
 
 # --------------------------------------------------------------------------------------

@@ -690,7 +690,8 @@ rr_fastfood16d_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// Wide blocks, d2 = 64 R with R in {8, 16, 32, 64} (512 .. 4096; FastFoodRBF on 256 < Xdim <= 4096), both arithmetics.
+// Wide blocks, d2 = 64 R with R in {8, 16, 32, 64} (512 .. 4096; FastFoodRBF, and FastFoodGM under wide_chain=True, on
+// 256 < Xdim <= 4096), both arithmetics.
 // ONE WAVE owns one (row, block) transform: element(lane, q) = (q / VW) * 64 VW + lane * VW + q % VW with VW = 16 bytes of
 // the compute type, so a lane's table loads, its LDS line writes and its stores are 16-byte vectors and the 64 lanes of a
 // group cover 1 KiB contiguous.  The WHT is separable over index bits: the log2(R) register bits are register butterflies
@@ -705,11 +706,21 @@ rr_fastfood16d_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, i
 template <typename TC>
 constexpr int ff64_waves(int R) { return 64 * R * (int)sizeof(TC) * 4 <= 65536 ? 4 : 2; }
 
-template <int R, bool PHI, bool VEC, typename TX, typename TC, typename TO>
+// GM (PHI only; rr_fastfood_create_wide_gm handles): one Gaussian spectral-mixture component, as in rr_fastfood16_kernel --
+//   out (N, 4 n) = [cos(VX + mX) | sin(VX + mX) | cos(VX - mX) | sin(VX - mX)] * scale,   mX = x . mean
+// with `mrev` = mean / 2 pi (d2 entries, zero beyond d): a fifth table, in registers under TAB and a fifth per-row load
+// otherwise.  mX is taken on the RAW x (not on x / l: a length scale beyond the float32 range must not reach it) in the loop
+// that forms v = x L, so x is read once: each lane folds its R elements into one accumulator by a chain of R FMAs (the first
+// onto zero), then a whole-wave all-reduce -- xor butterflies over the six lane bits, the partners of the WHT -- leaves the
+// same sum in every lane.  Longest rounding path of mX: R FMAs + 6 butterfly adds = R + 6 roundings (14, 22, 38, 70).
+// The phase is reduced modulo 1 AFTER the shift is added (ff_sincos_rev of ph + mX and of ph - mX).
+template <int R, bool PHI, bool VEC, typename TX, typename TC, typename TO, bool GM = false>
 __global__ void __launch_bounds__(ff64_waves<TC>(R) * 64)
 rr_fastfood64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, int k, const TC *__restrict__ Bm,
                      const TC *__restrict__ Gm, const int *__restrict__ PIm, const TC *__restrict__ Sm,
-                     const TC *__restrict__ invls, TO *__restrict__ out, int64_t ldo, TC scale, int rows_per_block) {
+                     const TC *__restrict__ invls, TO *__restrict__ out, int64_t ldo, TC scale, int rows_per_block,
+                     const TC *__restrict__ mrev = nullptr) {
+    static_assert(!GM || PHI, "the mixture component has features only");
     constexpr int D2 = 64 * R;
     constexpr int VW = 16 / (int)sizeof(TC);   // contiguous elements per lane and group
     constexpr int NG = R / VW;                 // groups of 64 VW elements
@@ -725,8 +736,8 @@ rr_fastfood64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, in
     const int j = blockIdx.x;
     const int n = D2 * k;
     const int lo = lane * VW;                  // element of register 0; register q: (q / VW) * 64 VW + lo + q % VW
-    // x rows hold d <= d2 elements; an output row holds n (VX) or 2 n (Phi) columns; one workgroup column per block
-    RR_DEV_ASSERT(d >= 1 && d <= D2 && d <= ldx && (PHI ? 2 : 1) * (int64_t)n <= ldo && j < k && (int)blockDim.x == WPB * 64 &&
+    // x rows hold d <= d2 elements; an output row holds n (VX), 2 n (Phi) or 4 n (GM) columns; one workgroup column per block
+    RR_DEV_ASSERT(d >= 1 && d <= D2 && d <= ldx && (GM ? 4 : PHI ? 2 : 1) * (int64_t)n <= ldo && j < k && (int)blockDim.x == WPB * 64 &&
                   (!VEC || (d % VW == 0 && ldx % VW == 0 && ldo % VW == 0)));
 
     // Group g of this lane's share of a table: one 16-byte load (8 bytes of PI next to float64 values).  Without TAB the
@@ -743,8 +754,8 @@ rr_fastfood64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, in
         return t;
     };
     // L = B / l (the +-1 diagonal folded into 1 / l: d2 entries of 1 / l, zero beyond d), G, S = S d2^-1.5 (/ 2 pi when PHI:
-    // the phase in revolutions) and PI
-    cvec Lv[TAB ? NG : 1], Gv[TAB ? NG : 1], Sv[TAB ? NG : 1];
+    // the phase in revolutions) and PI; GM: M = mean / 2 pi (d2 entries, zero beyond d)
+    cvec Lv[TAB ? NG : 1], Gv[TAB ? NG : 1], Sv[TAB ? NG : 1], Mv[TAB && GM ? NG : 1];
     ivec Pv[TAB ? NG : 1];
     if constexpr (TAB) {
 #pragma unroll
@@ -753,12 +764,14 @@ rr_fastfood64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, in
             Gv[g] = ld_c(Gb, g);
             Sv[g] = ld_c(Sb, g);
             Pv[g] = ld_p(g);
+            if constexpr (GM) Mv[g] = ld_c(mrev, g);
         }
     }
     auto tab_L = [&](int g) { return TAB ? Lv[TAB ? g : 0] : ld_c(invls, g) * ld_c(Bb, g); };
     auto tab_G = [&](int g) { return TAB ? Gv[TAB ? g : 0] : ld_c(Gb, g); };
     auto tab_S = [&](int g) { return TAB ? Sv[TAB ? g : 0] : ld_c(Sb, g); };
     auto tab_P = [&](int g) { return TAB ? Pv[TAB ? g : 0] : ld_p(g); };
+    auto tab_M = [&](int g) { return TAB ? Mv[TAB && GM ? g : 0] : ld_c(mrev, g); };  // (GM only)
     TC sg[4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) sg[b] = (lane >> b) & 1 ? TC(-1) : TC(1);
@@ -793,6 +806,21 @@ rr_fastfood64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, in
         fwht_stage<16, R, TC>(v, lane);
         fwht_stage<32, R, TC>(v, lane);
     };
+    // GM: the sum of a value over the 64 lanes, in every lane.  Lane bits 0-3: the DPP butterflies (float32: ONE asm statement
+    // with its wait states, row_allreduce16; float64: builtins, which the compiler pads), bits 4 and 5: the swaps of xor_partner
+    auto wave_allreduce = [&](TC t) {
+        if constexpr (F32) {
+            t = row_allreduce16(t);
+        } else {
+            t += dpp_partner64<1>(t);
+            t += dpp_partner64<2>(t);
+            t += dpp_partner64<4>(t);
+            t += dpp_partner64<8>(t);
+        }
+        t += xor_partner<16>(t);
+        t += xor_partner<32>(t);
+        return t;
+    };
     xvec xn[AHEAD ? NG : 1];
     if constexpr (AHEAD) {
 #pragma unroll
@@ -801,13 +829,20 @@ rr_fastfood64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, in
     for (; r < r1; r += WPB) {
         if constexpr (!TAB) asm volatile("" : "+v"(to));
         TC v[R];
+        TC mx = TC(0);  // GM: x . mean / 2 pi of this row (every lane holds the sum after the all-reduce)
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             const cvec l = tab_L(g);
             const xvec x = AHEAD ? xn[AHEAD ? g : 0] : load_xg(r, g);
 #pragma unroll
             for (int w = 0; w < VW; ++w) v[g * VW + w] = (TC)x[w] * l[w];
+            if constexpr (GM) {
+                const cvec m = tab_M(g);
+#pragma unroll
+                for (int w = 0; w < VW; ++w) mx = fma((TC)x[w], m[w], mx);
+            }
         }
+        if constexpr (GM) mx = wave_allreduce(mx);
         if constexpr (AHEAD) {
             const int64_t rn = r + WPB < r1 ? r + WPB : r;
 #pragma unroll
@@ -837,11 +872,19 @@ rr_fastfood64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, in
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             const cvec ss = tab_S(g);
-            TO o0[VW], o1[VW];
+            TO o0[VW], o1[VW], o2[GM ? VW : 1], o3[GM ? VW : 1];
 #pragma unroll
             for (int w = 0; w < VW; ++w) {
                 const TC ph = v[g * VW + w] * ss[w];
-                if constexpr (PHI) {
+                if constexpr (GM) {
+                    TC s, c;
+                    ff_sincos_rev<TC>(ph + mx, s, c);
+                    o0[w] = (TO)(c * scale);
+                    o1[w] = (TO)(s * scale);
+                    ff_sincos_rev<TC>(ph - mx, s, c);
+                    o2[w] = (TO)(c * scale);
+                    o3[w] = (TO)(s * scale);
+                } else if constexpr (PHI) {
                     TC s, c;
                     ff_sincos_rev<TC>(ph, s, c);
                     o0[w] = (TO)(c * scale);
@@ -863,6 +906,10 @@ rr_fastfood64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, int d, in
             };
             store(orow + g * 64 * VW, o0);
             if constexpr (PHI) store(orow + n + g * 64 * VW, o1);
+            if constexpr (GM) {  // column blocks 2, 3 = [cos | sin](VX - mX)
+                store(orow + 2 * (int64_t)n + g * 64 * VW, o2);
+                store(orow + 3 * (int64_t)n + g * 64 * VW, o3);
+            }
         }
     }
 }
@@ -929,26 +976,26 @@ static int ff_launch(rr_basis *b, const void *dX, int64_t N, int64_t ldx, void *
     const TC *Lm = (const TC *)(f32 ? (void *)b->ffL32 : (void *)b->ffL64);
     const TC *Mm = (const TC *)(f32 ? (void *)b->dmu32 : (void *)b->dmu64);  // GM: mean / 2 pi (ff_prepare_mean)
     const TC scale = (TC)(1.0 / sqrt((GM ? 2.0 : 1.0) * (double)b->n));
-    if (GM && (d2 < 16 || d2 > 256)) {
+    if (GM && (d2 < 16 || d2 > 256) && !b->ff_wide_gm) {
         rr_set_error("fastfood: the mixture-component chain kernel serves 16 <= d2 <= 256 (d2 = %d: use the dense route)", d2);
         return RR_ERR_UNSUPPORTED;
     }
-    if constexpr (!GM) {
-        if (d2 >= 512) {  // wide blocks (rr_fastfood_create_wide handles): one wave per (row, block)
+    {
+        if (d2 >= 512) {  // wide blocks (rr_fastfood_create_wide / _wide_gm handles; GM: the latter only): one wave per (row, block)
             constexpr int vw = 16 / (int)sizeof(TC);
             // the same conditions as the 16-lane families: rows, row widths and both pointers fit vw-element vectors
             const bool vec = (ldx % vw == 0) && (ldo % vw == 0) && (b->d % vw == 0) && ((uintptr_t)dX % (vw * sizeof(TX)) == 0) &&
                              ((uintptr_t)dOut % (vw * sizeof(TO)) == 0) && !getenv("RR_FF_NO_VEC");
 #define RR_FF64_(RR, VEC)                                                                                            \
     do {                                                                                                             \
-        auto kern = rr_fastfood64_kernel<RR, PHI, VEC, TX, TC, TO>;                                                  \
+        auto kern = rr_fastfood64_kernel<RR, PHI, VEC, TX, TC, TO, GM>;                                              \
         constexpr int threads = ff64_waves<TC>(RR) * 64;                                                             \
         static int occ = 0;                                                                                          \
         if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, threads, 0) != hipSuccess || occ < 1)) occ = 2; \
         const int64_t rp = ff_rows_per_wg(c, N, occ, k, true);                                                       \
-        RR_FF_LAUNCH_T(threads, "rr_fastfood64_kernel", RR, PHI, false, VEC, -1, kern,                               \
+        RR_FF_LAUNCH_T(threads, "rr_fastfood64_kernel", RR, PHI, GM, VEC, -1, kern,                                  \
                        dim3((unsigned)k, (unsigned)((N + rp - 1) / rp)), c->stream, (const TX *)dX, N, ldx, b->d, k, Bm, Gm,  \
-                       b->ffPI, Sm, Lm, (TO *)dOut, ldo, scale, (int)rp);                                            \
+                       b->ffPI, Sm, Lm, (TO *)dOut, ldo, scale, (int)rp, Mm);                                        \
     } while (0)
 #define RR_FF64(RR)                    \
     do {                               \
@@ -1177,8 +1224,9 @@ static int ff_host_call(rr_basis *b, const void *X, int x_dtype, int64_t N, int6
 }
 
 // rr_fastfood_create (d2 <= 256: the lane-major and lane-minor kernels, the mixture mode) and rr_fastfood_create_wide
-// (512 <= d2 <= 4096: rr_fastfood64_kernel, FastFoodRBF only) differ in the range they accept and in nothing else
-static int ff_create(const char *who, bool wide, rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B,
+// (512 <= d2 <= 4096: rr_fastfood64_kernel, FastFoodRBF only) differ in the range they accept and in nothing else;
+// rr_fastfood_create_wide_gm has the wide range and flags its handle for the wide kernel's mixture mode (4 d2 k columns)
+static int ff_create(const char *who, bool wide, bool gm, rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B,
                      const double *G, const int64_t *PI, const double *S, rr_basis **out) {
     RR_REQUIRE(ctx != nullptr && out != nullptr && B && G && PI && S, "%s: null argument", who);
     *out = nullptr;
@@ -1187,6 +1235,7 @@ static int ff_create(const char *who, bool wide, rr_ctx *ctx, int compute, int d
         RR_REQUIRE(d2 <= 4096, "%s: d2=%d > 4096 is not supported", who, d2);
         RR_REQUIRE(d2 > 256, "%s: d2=%d <= 256 is served by rr_fastfood_create", who, d2);
         RR_REQUIRE((int64_t)d2 * k <= INT32_MAX / 2, "%s: 2 d2 k = %lld columns exceed the int32 range", who, 2LL * d2 * k);
+        RR_REQUIRE(!gm || (int64_t)d2 * k <= INT32_MAX / 4, "%s: 4 d2 k = %lld columns exceed the int32 range", who, 4LL * d2 * k);
     } else {
         RR_REQUIRE(d2 <= 256, "%s: d2=%d > 256 is not supported yet", who, d2);
     }
@@ -1218,6 +1267,7 @@ static int ff_create(const char *who, bool wide, rr_ctx *ctx, int compute, int d
     b->n = d2 * k;
     b->ff_d2 = d2;
     b->ff_k = k;
+    b->ff_wide_gm = wide && gm;
     hipError_t e = hipSuccess;
 #define RR_UP(dst, vec)                                                                       \
     if (e == hipSuccess) e = hipMalloc((void **)&b->dst, (vec).size() * sizeof((vec)[0]));     \
@@ -1241,12 +1291,17 @@ extern "C" {
 
 int rr_fastfood_create(rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B, const double *G,
                        const int64_t *PI, const double *S, rr_basis **out) {
-    return ff_create("rr_fastfood_create", false, ctx, compute, d, d2, k, B, G, PI, S, out);
+    return ff_create("rr_fastfood_create", false, false, ctx, compute, d, d2, k, B, G, PI, S, out);
 }
 
 int rr_fastfood_create_wide(rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B, const double *G,
                             const int64_t *PI, const double *S, rr_basis **out) {
-    return ff_create("rr_fastfood_create_wide", true, ctx, compute, d, d2, k, B, G, PI, S, out);
+    return ff_create("rr_fastfood_create_wide", true, false, ctx, compute, d, d2, k, B, G, PI, S, out);
+}
+
+int rr_fastfood_create_wide_gm(rr_ctx *ctx, int compute, int d, int d2, int k, const int64_t *B, const double *G,
+                               const int64_t *PI, const double *S, rr_basis **out) {
+    return ff_create("rr_fastfood_create_wide_gm", true, true, ctx, compute, d, d2, k, B, G, PI, S, out);
 }
 
 int rr_fastfood_transform(rr_basis *b, const void *X, int x_dtype, int64_t N, int64_t ldx, const double *lenscale,

@@ -75,6 +75,7 @@ struct rr_basis {
     void *pass2d = nullptr;       // the same for f64 arithmetic
     // FastFood (kind == RR_KIND_FASTFOOD): (k, d2) diagonals / permutation, n = d2 * k
     int ff_d2 = 0, ff_k = 0;
+    bool ff_wide_gm = false;      // a rr_fastfood_create_wide_gm handle: the wide kernel's mixture mode serves it
     float *ffB32 = nullptr, *ffG32 = nullptr, *ffSrad32 = nullptr, *ffSrev32 = nullptr, *ffL32 = nullptr;
     double *ffB64 = nullptr, *ffG64 = nullptr, *ffSrad64 = nullptr, *ffSrev64 = nullptr, *ffL64 = nullptr;
     int *ffPI = nullptr;
