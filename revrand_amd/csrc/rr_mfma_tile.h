@@ -143,3 +143,28 @@ __device__ __forceinline__ void gram_consume_staggered(unsigned cur, floatx16 (&
 }
 #undef RR_PAIR
 
+// ---- one wave per SIMD: 128x128 per wave over a ring of four 16-row stages (rr_syrk_f32_w4_body, rr_rff.hip) ----
+constexpr int GW_SR = 16;                    // rows per ring stage: 4 k-step pairs
+constexpr int GW_STAGE = GW_SR * GR_LD;      // floats per stage (32 KiB)
+constexpr int GW_RING = 4;                   // stages
+
+// MFMA operands of one k-step pair for a 128x128 block: a[i] / b[j] = {k-step 2P, k-step 2P+1} of column block i / j.
+// Read IDX (0..7: a0..a3, b0..b3) of pair P of ring stage BUF.  ds_read2st64_b32's 8-bit offsets (units of 256 bytes, one
+// LDS row = 8) reach both stages of a ring half from one base: stage BUF & 1 starts 128 units in, row 4P + {0, 2} at 32 P + {0, 16}.
+struct KOps4 {
+    float2v a[4], b[4];
+    template <int BUF, int P, int IDX>
+    __device__ __forceinline__ void load_one(const unsigned (&abase)[2][4], const unsigned (&bbase)[2][4]) {
+        constexpr int O = (BUF & 1) * 128 + 32 * P;
+        static_assert(O + 16 <= 255, "ds_read2st64_b32 offset");
+        if constexpr (IDX < 4) a[IDX] = lds_read2st64<O, O + 16>(abase[BUF >> 1][IDX]);
+        else b[IDX - 4] = lds_read2st64<O, O + 16>(bbase[BUF >> 1][IDX - 4]);
+    }
+};
+// MFMA Q (0..31) of a k-step pair: k-step Q >> 4 (ascending, so every accumulator sees its rows in order), block (i, j)
+template <int Q>
+__device__ __forceinline__ void gram_w4_mfma(const KOps4 &o, floatx16 (&acc)[4][4]) {
+    constexpr int s = Q >> 4, i = (Q >> 2) & 3, j = Q & 3;
+    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.a[i][s], o.b[j][s], acc[i][j], 0, 0, 0);
+}
+

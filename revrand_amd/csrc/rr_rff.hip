@@ -257,7 +257,9 @@ rr_gm_grad_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, const TC *__
 //      with v_mfma_f32_32x32x2_f32, operands straight from LDS by conflict-free ds_read_b32
 //      (lane -> column, lane>>5 -> row of the 2-row k-step == the 32x32x2 A/B operand layout),
 //      prefetched one k-step ahead.  f32 accumulation inside a K-split, f64 atomics across
-//      K-splits into the upper triangle of G.
+//      K-splits into the upper triangle of G.  (That is rr_syrk_f32_body, today rr_syrk_f32_w8_kernel behind
+//      RR_SYRK_W8=1; the default body, rr_syrk_f32_w4_body, does the same work with 4 waves of 128x128 over a ring
+//      of four 16-row LDS stages -- see its comment.)
 //
 // Why two kernels: on gfx950 the f32-input MFMA runs at the f32 VALU rate and (measured:
 // SQ_VALU_MFMA_COEXEC_CYCLES = 0, produce/consume times purely additive) does not overlap with
@@ -889,11 +891,200 @@ __device__ __forceinline__ void rr_syrk_f32_body(const SyrkArgs &p, float *lds, 
         __shared__ float lds[2 * GR_KB * GR_LD];                                          \
         rr_syrk_f32_body<MODE>(p, lds, blockIdx.x);                                       \
     }
-RR_SYRK_KERNEL(rr_syrk_f32_kernel, 3)  // the default
+RR_SYRK_KERNEL(rr_syrk_f32_w8_kernel, 3)  // RR_SYRK_W8=1: the default before rr_syrk_f32_w4_body
 RR_SYRK_KERNEL(rr_syrk_f32_flat_kernel, 0)
 RR_SYRK_KERNEL(rr_syrk_f32_flatstag_kernel, 1)
 RR_SYRK_KERNEL(rr_syrk_f32_buf_kernel, 2)
 #undef RR_SYRK_KERNEL
+
+// ---------------------------------------------------------------------------------------
+// The same tile with ONE wave per SIMD (the structure of rr_syrk_b16w4_kernel, rr_syrk16.hip): 4 waves, wave (wr, wc) =
+// (wave >> 1, wave & 1) owns rows [128 wr, +128) of side A x columns [128 wc, +128) of side B in 16 accumulators (256 AGPRs).
+// With two waves per SIMD (the body above) both sit at every k-block barrier together, so neither covers the other's DMA
+// issue and operand reads; here a wave's own non-MFMA instructions -- 32 operand reads and 8 DMA requests per 128 MFMAs --
+// go one at a time into the shadow of its MFMAs (v_mfma_f32_32x32x2_f32 holds the pipe for 64 cycles; LDS and buffer
+// instructions issue beside it), and a 128x128 block needs 8 operand reads per 32 MFMAs instead of 6 per 16.
+//
+// LDS: a ring of four stages of 16 rows of the [row][256 | 256] tile (32 KiB each).  Step g (stage g in ring slot g & 3):
+//     s_barrier (g)
+//     4 k-step pairs x 32 MFMAs on stage g; behind them the reads of the next pair -- pairs 1..3 of stage g, then pair 0 of
+//     stage g+1 -- into the other register set, and this wave's 8 DMA requests for stage g+3 into slot (g + 3) & 3
+//     s_waitcnt vmcnt(8) lgkmcnt(0)
+// Why each access is legal:
+//   * reads of stage g+1 (pair 0 in step g, pairs 1..3 in step g+1): every wave waited for its requests of stage g+1 with
+//     the vmcnt(8) that ends step g-1 (only the 8 of stage g+2 may still fly) and then passed barrier g.  In the prologue:
+//     vmcnt(8) after the requests of stages 0..2, then a barrier, publish stages 0 and 1.
+//   * the DMA of step g overwrites slot (g - 1) & 3 = stage g-1, whose last reads (pair 3, issued in step g-1) every wave
+//     retired with the lgkmcnt(0) that ends step g-1, before barrier g.  Stage g+1's pair 0, read in step g, lies in slot
+//     (g + 1) & 3, which no request in flight (stages g+2, g+3) touches.
+// So the wave passes every barrier with its next 32 MFMAs' operands in registers and exposes no LDS latency there.
+// Past the end of the K-split (S stages, even, >= 2) the requests fetch the last stage again into a free slot and the reads
+// fetch operands nobody uses: the loop has no branch but its own, unrolled by the ring so that every LDS offset is an
+// immediate; S = 2 (mod 4) ends with half a turn.  An accumulator sees k-steps -- rows -- in ascending order, exactly as in
+// the 8-wave body: the per-split partial sums are the same fmaf chains, bit for bit.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ void rr_syrk_f32_w4_body(const SyrkArgs &p, float *lds, const unsigned bid) {  // lds: 4 x [16][512]
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    int tdx = bid % p.ntiles;
+    const int ks = bid / p.ntiles;
+    if (p.tile_map) tdx = p.tile_map[tdx];
+    int ta = 0;
+    const int od = p.offdiag_only;  // row ta then holds nb - ta - od tiles
+    while (tdx >= p.nb - ta - od) {
+        tdx -= p.nb - ta - od;
+        ++ta;
+    }
+    const int tb = ta + tdx + od;
+    const int ca = ta * GR_TC, cb = tb * GR_TC;
+
+    const int64_t row_begin = (int64_t)ks * p.rows_per_split;
+    int64_t row_end = row_begin + p.rows_per_split;
+    if (row_end > p.rows) row_end = p.rows;
+    const int S = (int)((row_end - row_begin) / GW_SR);  // stages: rows and splits are multiples of 32, so S is even
+    RR_DEV_ASSERT(p.rows % GR_KB == 0 && p.rows_per_split % GR_KB == 0 && tb < p.nb && p.nb * GR_TC <= p.ldp && S % 2 == 0);
+
+    // consumer role
+    const int wr = wave >> 1, wc_ = wave & 1;
+    const int l31 = lane & 31, h = lane >> 5;
+    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) float *)lds;
+    unsigned abase[2][4], bbase[2][4];  // [ring half][column block], bytes
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            abase[hf][i] = lds0 + 4u * (unsigned)(hf * 2 * GW_STAGE + h * GR_LD + wr * 128 + i * 32 + l31);
+            bbase[hf][i] = lds0 + 4u * (unsigned)(hf * 2 * GW_STAGE + h * GR_LD + GR_TC + wc_ * 128 + i * 32 + l31);
+        }
+    floatx16 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    if (S > 0) {
+        // DMA role: 32 requests of 1 KiB per stage; wave w moves rows 4 w .. 4 w + 3, request k = row k >> 1, side k & 1.
+        // Buffer-descriptor form (see rr_dma_kblock): the lane part is one constant VGPR, the stage goes into the descriptor's
+        // (scalar) base, row and side into a scalar offset -- no vector instruction per request.
+        const unsigned voff = 16u * lane;
+        const float *src_w = p.P + (row_begin + 4 * wave) * p.ldp + ca;  // wave-uniform
+        const int64_t stage_fl = (int64_t)GW_SR * p.ldp;
+        const unsigned ldp4 = (unsigned)p.ldp * 4u, dcol4 = (unsigned)(cb - ca) * 4u;  // ldp < 2^24 floats, cb >= ca
+        float *dst_w = lds + 4 * wave * GR_LD;
+        auto dma_stage = [&](int g) { return (int64_t)(g < S ? g : S - 1); };  // clamped: past the end the last stage is fetched again
+        // Every request's source row and columns, checked here and not inside dma_one: an assertion's slow path (printf)
+        // inside the pinned stream leaves the 256-accumulator loop no registers, and the compiler then spills the asm
+        // reads' destinations before their data has arrived.  dma_one below uses the same dma_stage(g) and row 4 w + (k >> 1).
+        for (int g = 0; g < S + 3; ++g)
+            for (int k = 0; k < 8; ++k)
+                RR_DEV_ASSERT(row_begin + dma_stage(g) * GW_SR + 4 * wave + (k >> 1) < row_end && row_end <= p.rows &&
+                              ca + GR_TC <= p.ldp && cb + GR_TC <= p.ldp);
+        auto dma_one = [&](int g, int slot, int k) {
+            const int64_t sc = dma_stage(g);
+            const rr_rsrc_t rs = rr_make_rsrc(src_w + sc * stage_fl, 0x7fffffffu);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)(dst_w + slot * GW_STAGE + (k >> 1) * GR_LD + (k & 1) * GR_TC), 16, voff,
+                                                     (unsigned)(k >> 1) * ldp4 + (unsigned)(k & 1) * dcol4, 0, 0);
+        };
+#pragma unroll
+        for (int st = 0; st < 3; ++st)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) dma_one(st, st, k);
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // stages 0 and 1 have landed
+        __builtin_amdgcn_s_barrier();
+        if (ta == tb && wr == 1 && wc_ == 0) {
+            // diagonal tile (nb_all = 1): this wave's 128x128 block lies below the diagonal.  It keeps its DMA duty and the
+            // barriers and issues no reads and no MFMAs.
+            for (int g = 0; g < S; ++g) {
+                __builtin_amdgcn_s_barrier();
+#pragma unroll
+                for (int k = 0; k < 8; ++k) dma_one(g + 3, (g + 3) & 3, k);
+                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            return;
+        }
+        KOps4 r0, r1;
+#define RR_F4_LOADALL(R, BUF, P)                                                                                   \
+    R.template load_one<BUF, P, 0>(abase, bbase); R.template load_one<BUF, P, 4>(abase, bbase);                    \
+    R.template load_one<BUF, P, 1>(abase, bbase); R.template load_one<BUF, P, 2>(abase, bbase);                    \
+    R.template load_one<BUF, P, 3>(abase, bbase); R.template load_one<BUF, P, 5>(abase, bbase);                    \
+    R.template load_one<BUF, P, 6>(abase, bbase); R.template load_one<BUF, P, 7>(abase, bbase);
+        RR_F4_LOADALL(r0, 0, 0)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        // MFMA Q of pair P, then ONE filler: operand read Q of the next pair (Q < 8), or DMA request 2 P (+ 1) of stage
+        // g + 3 (Q = 16, 24)
+#define RR_F4_M(Q, P, CUR, NXT, BUFN, PN)                                                           \
+    gram_w4_mfma<(Q)>(CUR, acc);                                                                    \
+    __builtin_amdgcn_sched_barrier(0);                                                              \
+    if constexpr ((Q) < 8) NXT.template load_one<BUFN, PN, (Q)>(abase, bbase);                      \
+    else if constexpr ((Q) == 16 || (Q) == 24) dma_one(g + 3, QD, 2 * (P) + ((Q) == 24 ? 1 : 0));   \
+    __builtin_amdgcn_sched_barrier(0);
+#define RR_F4_M8(Q, P, CUR, NXT, BUFN, PN)                                                                              \
+    RR_F4_M((Q), P, CUR, NXT, BUFN, PN) RR_F4_M((Q) + 1, P, CUR, NXT, BUFN, PN) RR_F4_M((Q) + 2, P, CUR, NXT, BUFN, PN) \
+    RR_F4_M((Q) + 3, P, CUR, NXT, BUFN, PN) RR_F4_M((Q) + 4, P, CUR, NXT, BUFN, PN) RR_F4_M((Q) + 5, P, CUR, NXT, BUFN, PN) \
+    RR_F4_M((Q) + 6, P, CUR, NXT, BUFN, PN) RR_F4_M((Q) + 7, P, CUR, NXT, BUFN, PN)
+        // pair P of the step's stage: its 32 MFMAs; the wait for ITS operands was the one before (pair 0: the end of the step before)
+#define RR_F4_PAIR(P, CUR, NXT, BUFN, PN)                                                           \
+    RR_F4_M8(0, P, CUR, NXT, BUFN, PN) RR_F4_M8(8, P, CUR, NXT, BUFN, PN)                           \
+    RR_F4_M8(16, P, CUR, NXT, BUFN, PN) RR_F4_M8(24, P, CUR, NXT, BUFN, PN)                         \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                              \
+    __builtin_amdgcn_sched_barrier(0);
+#define RR_F4_STEP(QQ)                                                                              \
+    {                                                                                               \
+        const int g = g0 + (QQ);                                                                    \
+        constexpr int QD = ((QQ) + 3) & 3;                                                          \
+        __builtin_amdgcn_s_barrier();                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                          \
+        RR_F4_PAIR(0, r0, r1, (QQ), 1)                                                              \
+        RR_F4_PAIR(1, r1, r0, (QQ), 2)                                                              \
+        RR_F4_PAIR(2, r0, r1, (QQ), 3)                                                              \
+        RR_F4_PAIR(3, r1, r0, (((QQ) + 1) & 3), 0)                                                  \
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                                            \
+        __builtin_amdgcn_sched_barrier(0);                                                          \
+    }
+        int g0 = 0;
+        for (; g0 + 4 <= S; g0 += 4) {
+            RR_F4_STEP(0)
+            RR_F4_STEP(1)
+            RR_F4_STEP(2)
+            RR_F4_STEP(3)
+        }
+        if (S & 2) {  // half a turn of the ring: slots 0 and 1 again
+            RR_F4_STEP(0)
+            RR_F4_STEP(1)
+        }
+#undef RR_F4_STEP
+#undef RR_F4_PAIR
+#undef RR_F4_M8
+#undef RR_F4_M
+#undef RR_F4_LOADALL
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped tail requests must land before the LDS is released
+    }
+
+    // ---- flush: f32 partial -> f64 G (upper triangle only) ----
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t gc = cb + wc_ * 128 + j * 32 + l31;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            asm volatile("" : "+a"(acc[i][j]));  // the block stays in its AGPRs up to here (else all 256 values move to VGPRs at once, and spill)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int64_t gr = ca + wr * 128 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                if (gr <= gc) rr_syrk_out(p, ks, gr, gc, acc[i][j][e]);
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256, 1) rr_syrk_f32_kernel(const SyrkArgs p) {  // the default
+    __shared__ __attribute__((aligned(16))) float lds[GW_RING * GW_STAGE];
+    rr_syrk_f32_w4_body(p, lds, blockIdx.x);
+}
 
 // ---------------------------------------------------------------------------------------
 // Ragged last column block (round 2).  When F is not a multiple of 256 the last column block holds only
@@ -2728,6 +2919,9 @@ int rr_launch_syrk_f32(rr_ctx *c, const float *P, int64_t rows, int64_t ldp, int
     // RR_SYRK_STAGGER = 0 / 1 / 2: the flat LDS-DMA of rounds 1-2 / the same staggered / buffer-descriptor requests right after
     // the barrier (A/B runs: 217.8 / 245 / 214.4 ms per 2M-row launch against 211.1 ms for the default, 3)
     static const int syrk_mode = getenv("RR_SYRK_STAGGER") ? atoi(getenv("RR_SYRK_STAGGER")) : 3;
+    // RR_SYRK_W8=1 (A/B runs): the 8-wave staggered body (two waves per SIMD, 128x64 per wave) in place of the default's
+    // one wave per SIMD (rr_syrk_f32_w4_body); the same per-split sums, bit for bit
+    static const bool syrk_w8 = getenv("RR_SYRK_W8") != nullptr && atoi(getenv("RR_SYRK_W8")) != 0;
     static const bool merge_diag = getenv("RR_SYRK_MERGE_DIAG") != nullptr && atoi(getenv("RR_SYRK_MERGE_DIAG")) != 0;
     if (merge_diag && od && !rg && ntiles > 0 && syrk_mode == 3 && !a.ablate && !getenv("RR_SYRK_NO_DIAG16")) {
         SyrkArgs ad = a;
@@ -2749,8 +2943,10 @@ int rr_launch_syrk_f32(rr_ctx *c, const float *P, int64_t rows, int64_t ldp, int
             hipLaunchKernelGGL(rr_syrk_f32_buf_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(GR_THREADS), 0, c->stream, a);
         else if (syrk_mode == 0 || a.ablate)  // (the ablation switches live in the flat variant)
             hipLaunchKernelGGL(rr_syrk_f32_flat_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(GR_THREADS), 0, c->stream, a);
+        else if (syrk_w8)
+            hipLaunchKernelGGL(rr_syrk_f32_w8_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(GR_THREADS), 0, c->stream, a);
         else
-            hipLaunchKernelGGL(rr_syrk_f32_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(GR_THREADS), 0, c->stream, a);
+            hipLaunchKernelGGL(rr_syrk_f32_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(256), 0, c->stream, a);
     }
     if (rg) {
         SyrkArgs ar = a;
