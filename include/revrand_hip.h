@@ -77,6 +77,19 @@ int64_t rr_debug_launch_checks(void);
  * library was loaded or the counts were last reset; name == NULL resets every count and returns 0.  -1 in a release
  * build, which does not count. */
 int64_t rr_debug_kernel_launches(const char *name);
+/* The plan a Gram launcher would execute for `rows` padded rows of a feature matrix of F columns and row length ldp on
+ * num_cu compute units, under the process' environment switches -- no context, no device call.  launcher: 0 = f32
+ * (flag: the rider column is present), 1 = f64 (flag: lower_tri), 2 = the split 16-bit engines (flag: fp16 operands;
+ * deterministic is ignored).  Fills out[0 .. min(nout, 22)) and returns 22 (a bad argument: RR_ERR_INVALID):
+ *   [0] 0, or the status the launcher would return (rr_last_error has its message)
+ *   [1] route: 0 small, 1 main, 2 merged, 3 f64, 4 split 16-bit     [2] column blocks     [3] nb     [4] ntiles
+ *   [5] od: diagonal tiles in a kernel of their own     [6] rg: ragged last block in a kernel of its own
+ *   [7] use_map: the XCD tile map     [8] deterministic slabs (0: atomics)     [9] rows the kernels walk
+ *   [10..13], [14..17], [18..21]: kernel, workgroups, rows per K-split and K-splits of the off-diagonal (or only), the
+ *   ragged and the diagonal kernel.  kernel: 0 none, 1 small, 2 main, 3 w8, 4 flat, 5 flatstag, 6 buf, 7 ragged,
+ *   8 diag, 9 diag16<32>, 10 diag16<64>, 11 merged (one launch of both parts), 12 f64, 13 f64 diag, 14 b16w4. */
+int rr_syrk_plan(int launcher, int64_t rows, int64_t ldp, int F, int flag, int num_cu, int deterministic, int64_t *out,
+                 int nout);
 const char *rr_last_error(void);
 int rr_device_count(int *count);
 

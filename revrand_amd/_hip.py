@@ -31,6 +31,8 @@ SIGNATURES = {
     "rr_build_flags": (ctypes.c_int, []),
     "rr_debug_launch_checks": (ctypes.c_int64, []),
     "rr_debug_kernel_launches": (ctypes.c_int64, [ctypes.c_char_p]),
+    "rr_syrk_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]),
     "rr_legacy_permutation": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "rr_legacy_randn": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_int, ctypes.c_int64, ctypes.c_int]),

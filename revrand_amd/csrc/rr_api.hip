@@ -1,6 +1,7 @@
 // Host side of the C ABI: contexts, device memory, basis objects.
 // See include/revrand_hip.h for the contract of every entry point.
 #include "rr_internal.h"
+#include "rr_syrk_plan.h"  // rr_syrk_plan
 #include <cstring>
 
 #include <cmath>
@@ -168,6 +169,24 @@ int rr_build_flags(void) {
 #else
     return 0;
 #endif
+}
+
+// The plan a Gram launcher would execute (rr_syrk_plan.h), flat: include/revrand_hip.h has the layout
+int rr_syrk_plan(int launcher, int64_t rows, int64_t ldp, int F, int flag, int num_cu, int deterministic, int64_t *out, int nout) {
+    RR_REQUIRE(launcher >= 0 && launcher <= 2 && rows >= 1 && ldp >= 1 && F >= 1 && num_cu >= 1 && out != nullptr && nout >= 0,
+               "rr_syrk_plan: bad argument");
+    const SyrkSwitches sw = rr_syrk_switches();
+    const SyrkPlan p = launcher == 0   ? rr_plan_syrk_f32(rows, ldp, F, flag, num_cu, deterministic, sw)
+                       : launcher == 1 ? rr_plan_syrk_f64(rows, ldp, F, flag, num_cu, deterministic, sw)
+                                       : rr_plan_syrk_split16(rows, ldp, F, flag, num_cu, sw);
+    if (p.err) rr_set_error("%s", p.msg);
+    const SyrkLaunch *l[3] = {&p.off, &p.ragged, &p.diag};
+    int64_t v[22] = {p.err, p.route, p.nb_all, p.nb, p.ntiles, p.od, p.rg, p.use_map ? 1 : 0, p.slabs, p.rows};
+    for (int i = 0; i < 3; ++i) {
+        v[10 + 4 * i] = l[i]->kernel; v[11 + 4 * i] = l[i]->grid; v[12 + 4 * i] = l[i]->rps; v[13 + 4 * i] = l[i]->nsplit;
+    }
+    for (int i = 0; i < 22 && i < nout; ++i) out[i] = v[i];
+    return 22;
 }
 
 const char *rr_last_error(void) { return g_last_error.c_str(); }

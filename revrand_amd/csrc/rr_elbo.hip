@@ -12,6 +12,7 @@
 // SYRK kernel's LDS-DMA / MFMA structure, plain f32 stores), rr_rowdot_kernel, rr_grad_t_kernel.
 #include "rr_internal.h"
 #include "rr_mfma_tile.h"
+#include "rr_syrk_args.h"  // rr_launch_syrk_f64
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -779,9 +780,6 @@ void rr_pass2_scratch_free(void *p) {
 int rr_features_rowmajor_f32(rr_basis *b, const void *dX, int x_dtype, int64_t m, int64_t mpad, int64_t ldx,
                              float *P, int64_t ldp, bool zero_pad_cols, float *Pt = nullptr, int64_t ldt = 0,
                              bool *pt_written = nullptr, double scale_mult = 1.0);  // rr_rff.hip
-int rr_launch_gemm_tn_bf16(rr_ctx *c, int nprod, const float *A, int64_t lda, const float *B, int64_t ldb, float *D,
-                           int64_t ldd, int64_t K, int64_t M, int64_t N, void *sa, void *sb, bool sb_ready,
-                           bool upper_b = false);  // rr_syrk16.hip
 
 template <typename TX>
 static int launch_features_t(rr_basis *b, const TX *X, int64_t N, int64_t Npad, int64_t ldx, const float *m32,
@@ -4219,8 +4217,6 @@ void rr_glm_sgd_destroy(rr_glm_sgd *o) {
 // pass2_run64: every child writes its column block, P^T by a transposing pass, U = P C on rr_gemm_tn_f64_kernel, the
 // float64 epilogue kernels above.  Written for the resident fit (CatFitState): no GLM step, no split engines.
 // =============================================================================================
-int rr_launch_syrk_f64(rr_ctx *c, const double *P, int64_t rows, int64_t ldp, int F, double *dG, int lower_tri = 0);  // rr_rff.hip
-
 // (struct rr_featmat64: rr_internal.h -- the centre bases' float64 entry points of rr_centres.hip share it)
 
 template <typename TX>

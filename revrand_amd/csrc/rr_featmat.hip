@@ -3,12 +3,11 @@
 // (BasisCat.transform's hstack, basis_functions.py:1599-1627, without leaving the GPU), then reduced
 // to Phi^T Phi / Phi^T y (slm.py:146,157).
 #include "rr_internal.h"
+#include "rr_syrk_args.h"  // rr_launch_syrk_f32
 
 int rr_features_rowmajor_f32(rr_basis *b, const void *dX, int x_dtype, int64_t m, int64_t mpad, int64_t ldx,
                              float *P, int64_t ldp, bool zero_pad_cols, float *Pt = nullptr, int64_t ldt = 0,
                              bool *pt_written = nullptr, double scale_mult = 1.0);
-int rr_launch_syrk_f32(rr_ctx *c, const float *P, int64_t rows, int64_t ldp, int F, double *dG, hipEvent_t mid,
-                       double *bcol = nullptr);
 
 
 // [1, X] or X (LinearBasis.transform, basis_functions.py:468-485) into columns [col0, col0 + d + onescol)

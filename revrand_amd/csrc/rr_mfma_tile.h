@@ -4,14 +4,13 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdlib>
+#include "rr_syrk_plan.h"  // GR_TC, GR_KB
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(1))) const void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
 
-constexpr int GR_TC = 256;   // columns per tile side
-constexpr int GR_KB = 32;    // rows per k-block
-constexpr int GR_LD = 512;   // LDS tile row length (floats): [A side 256 | B side 256]
+constexpr int GR_LD = 512;  // LDS tile row length (floats): [A side 256 | B side 256]
 constexpr int GR_THREADS = 512;
 
 typedef float float2v __attribute__((ext_vector_type(2)));

@@ -14,10 +14,10 @@
 #include <cmath>
 
 #include "rr_internal.h"
+#include "rr_syrk_args.h"  // rr_launch_syrk_f64
 
 int rr_launch_gemm_tn_f64(rr_ctx *c, const double *A, int64_t lda, const double *B, int64_t ldb, double *D, int64_t ldd,
                           int64_t K, int64_t M, int64_t N, int subtract, int upper_only);             // rr_rff.hip
-int rr_launch_syrk_f64(rr_ctx *c, const double *P, int64_t rows, int64_t ldp, int F, double *dG, int lower_tri = 0);  // rr_rff.hip
 
 constexpr int PB = 128;  // panel width = the f64 GEMM tile
 

@@ -1537,7 +1537,7 @@ rr_syrk_f32_diag16_kernel(const SyrkArgs p) {
 // through registers into a double-buffered LDS tile [32][A 128 | B 128]; diagonal tiles compute the whole block and keep
 // gr <= gc; the rider column (Phi^T y, column F) and the deterministic slabs go through rr_syrk_out as in the big kernels.
 // ---------------------------------------------------------------------------------------
-constexpr int GS_TC = 128, GS_KB = 32, GS_LD = 2 * GS_TC, GS_THREADS = 256;
+constexpr int GS_LD = 2 * GS_TC, GS_THREADS = 256;  // (GS_TC, GS_KB: rr_syrk_plan.h)
 
 __global__ void __launch_bounds__(GS_THREADS, 2)
 rr_syrk_f32_small_kernel(const SyrkArgs p) {
@@ -1634,8 +1634,6 @@ rr_syrk_f32_merged_kernel(const SyrkArgs p, const SyrkArgs pd, const unsigned n_
 // f64 with the row stride padded by 128 B so that the 4 rows of a k-step fall on different
 // bank halves (conflict-free ds_read_b64), two workgroups per CU (68 KiB of LDS each).
 // ---------------------------------------------------------------------------------------
-constexpr int G64_TC = 128;            // columns per tile side
-constexpr int G64_KB = 16;             // rows per k-block
 constexpr int G64_LDB = 2 * G64_TC * 8 + 128;  // LDS row stride in bytes (2048 + 128 pad)
 constexpr int G64_THREADS = 256;
 
@@ -2653,391 +2651,92 @@ static int ensure_zbuf(rr_basis *b, size_t bytes) {
     return RR_OK;
 }
 
-// Greedy XCD-aware tile order: dispatch position q goes to XCD q % 8, so XCD x receives positions
-// x, x+8, ...; fill each XCD's quota with tiles that add the fewest new column blocks to the set it
-// already reads.  Only used when ntiles is a multiple of 8 (equal quotas keep the load balanced).
-static void rr_build_tile_map_uncached(int nb, int od, int nxcd, std::vector<int> &map);
+// ---- the Gram launchers: each asks rr_syrk_plan.h for the route, the tile order and the K-splits, and launches that ----
 
-void rr_build_tile_map(int nb, int od, int nxcd, std::vector<int> &map) {
-    static std::mutex mu;
-    static std::map<int, std::vector<int>> cache;  // contexts of one process (device groups, alternating bases) share the maps
-    std::lock_guard<std::mutex> lk(mu);
-    const int key = (nb * 2 + od) * 64 + nxcd;
-    auto it = cache.find(key);
-    if (it == cache.end()) {
-        std::vector<int> m;
-        rr_build_tile_map_uncached(nb, od, nxcd, m);
-        it = cache.emplace(key, std::move(m)).first;
-    }
-    map = it->second;
+// deterministic mode: the plan's slabs of ldp x ldp partials, one per K-split, from the context's scratch ...
+template <typename T>
+static int syrk_det_slabs(rr_ctx *c, const SyrkPlan &pl, int64_t ldp, T **part, int64_t *stride) {
+    void *slabs = nullptr;
+    const int rc = pl.slabs ? rr_det_scratch(c, (size_t)pl.slabs * (size_t)ldp * (size_t)ldp * sizeof(T), &slabs) : RR_OK;
+    if (slabs) *part = (T *)slabs, *stride = ldp * ldp;
+    return rc;
 }
 
-static void rr_build_tile_map_uncached(int nb, int od, int nxcd, std::vector<int> &map) {
-    const int ntiles = od ? nb * (nb - 1) / 2 : nb * (nb + 1) / 2;
-    map.assign(ntiles, 0);
-    std::vector<int> ta(ntiles), tb(ntiles);
-    for (int a = 0, t = 0; a < nb; ++a)
-        for (int b2 = a + od; b2 < nb; ++b2, ++t) { ta[t] = a; tb[t] = b2; }
-    std::vector<char> used(ntiles, 0);
-    const int quota = ntiles / nxcd;
-    std::vector<int> part(ntiles, 0);  // tile -> XCD
-    // greedy start: every XCD in turn takes the tiles that add the fewest new column blocks to what it already reads
-    for (int x = 0; x < nxcd; ++x) {
-        std::vector<char> have(nb, 0);
-        for (int s = 0; s < quota; ++s) {
-            int best = -1, bestcost = 1 << 30;
-            for (int t = 0; t < ntiles; ++t) {
-                if (used[t]) continue;
-                const int cost = (have[ta[t]] ? 0 : 1) + ((have[tb[t]] || tb[t] == ta[t]) ? 0 : 1);
-                if (cost < bestcost) { bestcost = cost; best = t; }
-            }
-            used[best] = 1;
-            have[ta[best]] = have[tb[best]] = 1;
-            part[best] = x;
-        }
-    }
-    // ... improved by annealing over tile SWAPS between XCDs (round 5; RR_GRAM_TILE_ANNEAL=0: the greedy map).  The cost is
-    // what the eight L2s read per row split: the number of distinct column blocks of P each XCD's tiles touch, summed --
-    // 65 for the greedy partition of F = 4096's 120 off-diagonal tiles, 57 after annealing (a (16, 6, 1) design, 48, does not
-    // exist); 141 -> 130 at 32 column blocks.  Deterministic (fixed seed); made once per process and tile count (cache below).
-    static const bool anneal = !(getenv("RR_GRAM_TILE_ANNEAL") && atoi(getenv("RR_GRAM_TILE_ANNEAL")) == 0);
-    if (anneal && nxcd > 1 && ntiles >= 2 * nxcd && nb <= 128) {
-        std::vector<int> cnt((size_t)nxcd * nb, 0);
-        auto add = [&](int x, int t, int d) {
-            cnt[(size_t)x * nb + ta[t]] += d;
-            if (tb[t] != ta[t]) cnt[(size_t)x * nb + tb[t]] += d;
-        };
-        for (int t = 0; t < ntiles; ++t) add(part[t], t, 1);
-        auto cost_of = [&]() {
-            int c2 = 0;
-            for (size_t i = 0; i < cnt.size(); ++i) c2 += cnt[i] > 0;
-            return c2;
-        };
-        // blocks of XCD x in use if tile `out` leaves and tile `in` joins
-        auto delta_one = [&](int x, int out, int in) {
-            int before = 0, after = 0;
-            const int bl[4] = {ta[out], tb[out], ta[in], tb[in]};
-            for (int i = 0; i < 4; ++i) {
-                bool seen = false;
-                for (int j = 0; j < i; ++j) seen = seen || bl[j] == bl[i];
-                if (seen) continue;
-                const int b = bl[i];
-                const int c0 = cnt[(size_t)x * nb + b];
-                const int c1 = c0 - ((ta[out] == b) || (tb[out] == b) ? 1 : 0) + ((ta[in] == b) || (tb[in] == b) ? 1 : 0);
-                before += c0 > 0;
-                after += c1 > 0;
-            }
-            return after - before;
-        };
-        uint64_t rng = 0x9E3779B97F4A7C15ull;
-        auto next = [&]() {
-            rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17;
-            return rng;
-        };
-        int cur = cost_of(), best = cur;
-        std::vector<int> best_part = part;
-        const int64_t iters = std::min<int64_t>((int64_t)20000 * ntiles, 6000000);  // 0.1 s at F = 4096, 0.3 s at most
-        for (int64_t it = 0; it < iters; ++it) {
-            const int t1 = (int)(next() % (uint64_t)ntiles), t2 = (int)(next() % (uint64_t)ntiles);
-            const int x = part[t1], y = part[t2];
-            if (x == y) continue;
-            const int d = delta_one(x, t1, t2) + delta_one(y, t2, t1);
-            const double temp = 0.4 * (1.0 - (double)it / (double)iters) + 0.05;
-            if (d <= 0 || (double)(next() >> 11) / 9007199254740992.0 < exp(-(double)d / temp)) {
-                add(x, t1, -1); add(y, t2, -1); add(x, t2, 1); add(y, t1, 1);
-                part[t1] = y; part[t2] = x;
-                cur += d;
-                if (cur < best) { best = cur; best_part = part; }
-            }
-        }
-        part = best_part;
-    }
-    // launch order: workgroup s * nxcd + x runs on XCD x; an XCD's tiles in (a, b) order, so that neighbours in time share blocks
-    std::vector<int> fill(nxcd, 0);
-    for (int t = 0; t < ntiles; ++t) map[(size_t)fill[part[t]]++ * nxcd + part[t]] = t;
+// ... and their ordered reduction into G (f32: and the rider's column into bcol), queued behind the kernels (<float> is
+// instantiated here, ahead of the launchers: rr_syrk_det_reduce_kernel<float> keeps its place in the code object)
+template <typename T>
+static void syrk_det_reduce(rr_ctx *c, const SyrkPlan &pl, const T *part, int64_t ldp, int F, double *dG, double *bcol) {
+    if (!part) return;
+    const int cols = F + (sizeof(T) == 4 ? 1 : 0);
+    hipLaunchKernelGGL(rr_syrk_det_reduce_kernel<T>, dim3((unsigned)((cols + 255) / 256), (unsigned)F), dim3(256), 0, c->stream,
+                       part, ldp * ldp, ldp, F, (int)pl.slabs, dG, bcol);
 }
+template void syrk_det_reduce<float>(rr_ctx *, const SyrkPlan &, const float *, int64_t, int, double *, double *);
 
 // G(upper) += P^T P for a zero-padded f32 feature matrix (rows % 32 == 0, ldp % 256 == 0).
-
-int rr_launch_syrk_f32(rr_ctx *c, const float *P, int64_t rows, int64_t ldp, int F, double *dG, hipEvent_t mid,
-                       double *bcol = nullptr) {
-    if (c->gram_engine != 0) {
-        RR_REQUIRE(bcol == nullptr, "gram: the rider column needs the f32 engine");
-        RR_REQUIRE(!c->deterministic, "gram: deterministic mode (rr_set_deterministic) needs the f32 engine, not a split 16-bit one");
-        return rr_launch_syrk_bf16(c, c->gram_engine, P, nullptr, rows, ldp, F, dG, mid);
-    }
-    RR_REQUIRE(bcol == nullptr || F < ldp, "gram: no pad column for the rider");
-    // small feature counts over few rows: 128 x 128 tiles (rr_syrk_f32_small_kernel); RR_SYRK_SMALL=0: never (A/B runs)
-    static const bool small_off = getenv("RR_SYRK_SMALL") != nullptr && atoi(getenv("RR_SYRK_SMALL")) == 0;
-    // (where it wins, tools/small_gram_bench.py: while the 256 x 256 tiles x 1024-row splits cannot give every CU a workgroup --
-    // F = 512: up to ~85 000 rows (10 000 rows: 0.148 against 0.200 ms per pass), F = 1024: up to ~26 000; above that the big
-    // tiles' LDS-DMA pipeline is 2-3x faster per flop than this kernel's register-staged loads)
-    const int64_t big_tiles = (ldp / GR_TC) * (ldp / GR_TC + 1) / 2;
-    if (!small_off && ldp <= 1024 && big_tiles * ((rows + 1023) / 1024) < c->num_cu && rows % GS_KB == 0 && !getenv("RR_GRAM_ABLATE")) {
-        const int nbs = (int)(ldp / GS_TC), nt = nbs * (nbs + 1) / 2;
-        // K-splits: enough workgroups for every CU (two fit one), at least 128 rows and at most 32768 each
-        int64_t ns = std::max<int64_t>((2 * c->num_cu + nt - 1) / nt, (rows + 32767) / 32768);
-        ns = std::min<int64_t>(ns, std::max<int64_t>(rows / 128, 1));
-        const int64_t rps_s = ((rows + ns - 1) / ns + GS_KB - 1) / GS_KB * GS_KB;
-        ns = (rows + rps_s - 1) / rps_s;
-        SyrkArgs a;
-        a.P = P; a.rows = rows; a.ldp = ldp; a.F = F; a.nb = nbs; a.ntiles = nt; a.rows_per_split = rps_s; a.G = dG;
-        a.bcol = bcol; a.tile_map = nullptr; a.offdiag_only = 0; a.ablate = 0;
-        if (c->deterministic) {
-            void *slabs = nullptr;
-            int rc = rr_det_scratch(c, (size_t)ns * (size_t)ldp * (size_t)ldp * sizeof(float), &slabs);
-            if (rc != RR_OK) return rc;
-            a.part = (float *)slabs;
-            a.part_stride = ldp * ldp;
-        }
-        hipLaunchKernelGGL(rr_syrk_f32_small_kernel, dim3((unsigned)(ns * nt)), dim3(GS_THREADS), 0, c->stream, a);
-        if (mid) RR_CHECK_HIP(hipEventRecord(mid, c->stream));
-        if (a.part)
-            hipLaunchKernelGGL(rr_syrk_det_reduce_kernel<float>, dim3((unsigned)((F + 1 + 255) / 256), (unsigned)F), dim3(256), 0,
-                               c->stream, a.part, a.part_stride, ldp, F, (int)ns, dG, bcol);
-        RR_CHECK_HIP(hipGetLastError());
-        return RR_OK;
-    }
-    const int nb_all = (int)(ldp / GR_TC);
-    const int od = (nb_all >= 2 && !getenv("RR_SYRK_NO_DIAG_KERNEL")) ? 1 : 0;  // diagonal tiles in their own kernel
-    // ragged last block (<= 192 valid columns): its off-diagonal tiles go to rr_syrk_f32_ragged_kernel, and the main
-    // kernel enumerates the tiles among the first nb_all - 1 blocks only
-    const int w_last = F + (bcol ? 1 : 0) - GR_TC * (nb_all - 1);
-    const int rg = (od && nb_all >= 3 && w_last <= 192 && !getenv("RR_SYRK_NO_RAGGED_KERNEL")) ? 1 : 0;
-    const int nb = nb_all - rg;
-    const int ntiles = od ? nb * (nb - 1) / 2 : nb * (nb + 1) / 2;
-    const int nxcd = 8;
-    const bool use_map = (ntiles % nxcd == 0) && !getenv("RR_GRAM_NO_TILE_MAP");
-    if (use_map && c->tile_map_nb != nb * 2 + od) {
-        std::vector<int> map;
-        rr_build_tile_map(nb, od, nxcd, map);
-        if (c->tile_map) (void)hipFree(c->tile_map);
-        c->tile_map = nullptr;
-        RR_CHECK_HIP(hipMalloc((void **)&c->tile_map, map.size() * sizeof(int)));
-        RR_CHECK_HIP(hipMemcpy(c->tile_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-        c->tile_map_nb = nb * 2 + od;
-    }
-    // K-splits: f32 accumulation over <= 32768 rows per split.  Workgroups of one kernel all cost the same, so
-    // each kernel gets the split count that makes ITS workgroup count (close to) a multiple of the CU count:
-    // exactly for the off-diagonal kernel (nsplit = k * CUs / gcd(CUs, ntiles), k minimal), by search for the
-    // diagonal one (nb workgroups per split; an odd nb would otherwise force CUs splits on both).
-    const int64_t total_tiles = (int64_t)nb_all * (nb_all + 1) / 2;
-    auto gcd64 = [](int64_t x, int64_t y) { while (y) { const int64_t u = x % y; x = y; y = u; } return x; };
-    const int64_t min_splits = (rows + 32767) / 32768;
-    auto rows_per = [&](int64_t ns) { return ((rows + ns - 1) / ns + GR_KB - 1) / GR_KB * GR_KB; };
-    const int64_t unit = ntiles > 0 ? c->num_cu / gcd64(c->num_cu, ntiles) : 1;
-    int64_t nsplit = (min_splits + unit - 1) / unit * unit;
-    // small inputs: just cover the rows, >= 1024 per split -- unless that leaves most CUs without a workgroup (few tiles:
-    // config 1's F = 512 is ONE off-diagonal tile and two diagonal ones, 10 splits of its 10 000 rows = 10 workgroups of
-    // 32 k-blocks at one CU's rate each): then down to 256 rows per split, until the tiles x splits fill the CUs
-    // (config 1's `_elbo`: 1.42 -> 1.13 ms)
-    auto floor_rows = [&](int64_t tiles_per_split) {
-        return tiles_per_split * ((rows + 1023) / 1024) < c->num_cu ? (int64_t)256 : (int64_t)1024;
-    };
-    auto small_split = [&](int64_t tiles_per_split) {
-        const int64_t fr = floor_rows(tiles_per_split);
-        if (fr == 1024) return (rows + 1023) / 1024;
-        const int64_t want = (c->num_cu + tiles_per_split - 1) / std::max<int64_t>(tiles_per_split, 1);
-        return std::min((rows + fr - 1) / fr, std::max((rows + 1023) / 1024, want));
-    };
-    if (rows / nsplit < 1024) {
-        nsplit = small_split(std::max(ntiles, 1));
-        // (round 6) ... and among the split counts around it, the one whose workgroups finish soonest: time ~ rounds x (rows per
-        // split + a workgroup's prologue and 64k-entry atomic epilogue, ~96 rows' worth).  F = 1024, N = 44 484 (the reference's
-        // SARCOS shape): 44 splits x 6 tiles = 264 workgroups were TWO rounds on 256 CUs, the second with 8 workgroups.
-        static const bool no_search = getenv("RR_SYRK_SPLIT_SEARCH") != nullptr && atoi(getenv("RR_SYRK_SPLIT_SEARCH")) == 0;
-        if (ntiles > 0 && !no_search) {
-            double best_cost = 1e300;
-            int64_t best_ns = nsplit;
-            const int64_t ns_hi = std::max<int64_t>(rows / 256, 1), ns_lo = std::max<int64_t>(rows / 32768, 1);
-            for (int64_t ns = ns_lo; ns <= ns_hi && ns <= ns_lo + 4096; ++ns) {
-                const int64_t rp = rows_per(ns), n2 = (rows + rp - 1) / rp;
-                const int64_t rounds = ((int64_t)ntiles * n2 + c->num_cu - 1) / c->num_cu;
-                const double cost = (double)rounds * ((double)rp + 96.0);
-                if (cost < best_cost - 1e-9) {
-                    best_cost = cost;
-                    best_ns = n2;
-                }
-            }
-            nsplit = best_ns;
-        }
-    }
-    if (nsplit < 1) nsplit = 1;
-    int64_t rps = rows_per(nsplit);
-    int64_t nsplit_d = nsplit, rps_d = rps;
-    if (od) {
-        double best = -1.0;
-        for (int64_t ns = min_splits; ns < min_splits + 96; ++ns) {
-            if (rows / ns < floor_rows(nb_all) && ns > 1) break;
-            const int64_t wg = ns * nb_all, rounds = (wg + c->num_cu - 1) / c->num_cu;
-            const double eff = (double)wg / (double)(rounds * c->num_cu);
-            if (eff > best + 1e-9) {
-                best = eff;
-                nsplit_d = ns;
-            }
-        }
-        rps_d = rows_per(nsplit_d);
-        if (rows % 64 == 0 && getenv("RR_SYRK_DIAG_KB") != nullptr && atoi(getenv("RR_SYRK_DIAG_KB")) == 64)
-            rps_d = (rps_d + 63) / 64 * 64;  // whole 64-row k-blocks for rr_syrk_f32_diag16_kernel<64>
-    }
-    int64_t nsplit_r = nsplit, rps_r = rps;
-    if (rg) {  // nb_all - 1 equal-cost workgroups per split: the split count whose workgroups fill whole rounds best
-        double best = -1.0;
-        for (int64_t ns = min_splits; ns < min_splits + 96; ++ns) {
-            if (rows / ns < floor_rows(nb_all - 1) && ns > 1) break;
-            const int64_t wg = ns * (nb_all - 1), rounds = (wg + c->num_cu - 1) / c->num_cu;
-            const double eff = (double)wg / (double)(rounds * c->num_cu);
-            if (eff > best + 1e-9) {
-                best = eff;
-                nsplit_r = ns;
-            }
-        }
-        rps_r = rows_per(nsplit_r);
-    }
-    const char *renv = getenv("RR_GRAM_ROWS_PER_SPLIT");
-    if (renv && atoll(renv) >= GR_KB) rps = rps_d = rps_r = (atoll(renv) / GR_KB) * GR_KB;
-    if (c->deterministic) rps_d = rps_r = rps;  // one slab per K-split, shared by the three kernels
-    nsplit = (rows + rps - 1) / rps;
-    nsplit_d = (rows + rps_d - 1) / rps_d;
-    nsplit_r = (rows + rps_r - 1) / rps_r;
-    RR_REQUIRE(nsplit * total_tiles < (int64_t)1 << 31 && nsplit_d * nb_all < (int64_t)1 << 31 &&
-                   nsplit_r * nb_all < (int64_t)1 << 31, "gram: grid too large");
+int rr_launch_syrk_f32(rr_ctx *c, const float *P, int64_t rows, int64_t ldp, int F, double *dG, hipEvent_t mid, double *bcol) {
+    const SyrkPlan pl = rr_plan_syrk_f32(rows, ldp, F, bcol != nullptr, c->num_cu, c->deterministic, rr_syrk_switches(), c->gram_engine);
+    if (pl.err) return rr_syrk_plan_status(pl);
+    if (pl.route == SR_SPLIT16) return rr_launch_syrk_bf16(c, c->gram_engine, P, nullptr, rows, ldp, F, dG, mid);
+    int rc = pl.use_map ? rr_syrk_tile_map(c, pl.nb, pl.od) : RR_OK;
+    if (rc != RR_OK) return rc;
     SyrkArgs a;
-    a.P = P; a.rows = rows; a.ldp = ldp; a.F = F; a.nb = nb; a.ntiles = ntiles; a.rows_per_split = rps; a.G = dG;
+    a.P = P; a.rows = rows; a.ldp = ldp; a.F = F; a.nb = pl.nb; a.ntiles = pl.ntiles; a.rows_per_split = pl.off.rps; a.G = dG;
     a.bcol = bcol;
-    a.tile_map = use_map ? c->tile_map : nullptr;
-    a.offdiag_only = od;
-    a.ablate = getenv("RR_GRAM_ABLATE") ? atoi(getenv("RR_GRAM_ABLATE")) : 0;
-    a.spread = rr_dma_spread_env();
-    if (c->deterministic) {
-        void *slabs = nullptr;
-        int rc = rr_det_scratch(c, (size_t)nsplit * (size_t)ldp * (size_t)ldp * sizeof(float), &slabs);
-        if (rc != RR_OK) return rc;
-        a.part = (float *)slabs;
-        a.part_stride = ldp * ldp;
+    a.tile_map = pl.use_map ? c->tile_map : nullptr;
+    a.offdiag_only = pl.od;
+    a.ablate = pl.ablate;
+    if (pl.route != SR_SMALL) a.spread = rr_dma_spread_env();
+    rc = syrk_det_slabs(c, pl, ldp, &a.part, &a.part_stride);
+    if (rc != RR_OK) return rc;
+    SyrkArgs ad = a;  // the diagonal and ragged kernels: every column block, K-splits of their own
+    ad.nb = pl.nb_all;
+    ad.rows_per_split = pl.diag.rps;
+    const dim3 g_off((unsigned)pl.off.grid), g_diag((unsigned)pl.diag.grid);
+    switch (pl.off.kernel) {
+    case SK_F32_SMALL: hipLaunchKernelGGL(rr_syrk_f32_small_kernel, g_off, dim3(GS_THREADS), 0, c->stream, a); break;
+    case SK_F32_MERGED:
+        hipLaunchKernelGGL(rr_syrk_f32_merged_kernel, dim3(g_off.x + g_diag.x), dim3(GR_THREADS), 0, c->stream, a, ad, g_off.x);
+        break;
+    case SK_F32_FLATSTAG: hipLaunchKernelGGL(rr_syrk_f32_flatstag_kernel, g_off, dim3(GR_THREADS), 0, c->stream, a); break;
+    case SK_F32_BUF: hipLaunchKernelGGL(rr_syrk_f32_buf_kernel, g_off, dim3(GR_THREADS), 0, c->stream, a); break;
+    case SK_F32_FLAT: hipLaunchKernelGGL(rr_syrk_f32_flat_kernel, g_off, dim3(GR_THREADS), 0, c->stream, a); break;
+    case SK_F32_W8: hipLaunchKernelGGL(rr_syrk_f32_w8_kernel, g_off, dim3(GR_THREADS), 0, c->stream, a); break;
+    case SK_F32_MAIN: hipLaunchKernelGGL(rr_syrk_f32_kernel, g_off, dim3(256), 0, c->stream, a); break;
     }
-    // RR_SYRK_STAGGER = 0 / 1 / 2: the flat LDS-DMA of rounds 1-2 / the same staggered / buffer-descriptor requests right after
-    // the barrier (A/B runs: 217.8 / 245 / 214.4 ms per 2M-row launch against 211.1 ms for the default, 3)
-    static const int syrk_mode = getenv("RR_SYRK_STAGGER") ? atoi(getenv("RR_SYRK_STAGGER")) : 3;
-    // RR_SYRK_W8=1 (A/B runs): the 8-wave staggered body (two waves per SIMD, 128x64 per wave) in place of the default's
-    // one wave per SIMD (rr_syrk_f32_w4_body); the same per-split sums, bit for bit
-    static const bool syrk_w8 = getenv("RR_SYRK_W8") != nullptr && atoi(getenv("RR_SYRK_W8")) != 0;
-    static const bool merge_diag = getenv("RR_SYRK_MERGE_DIAG") != nullptr && atoi(getenv("RR_SYRK_MERGE_DIAG")) != 0;
-    if (merge_diag && od && !rg && ntiles > 0 && syrk_mode == 3 && !a.ablate && !getenv("RR_SYRK_NO_DIAG16")) {
-        SyrkArgs ad = a;
-        ad.nb = nb_all;
-        ad.rows_per_split = rps_d;
-        const unsigned n_off = (unsigned)(nsplit * ntiles);
-        hipLaunchKernelGGL(rr_syrk_f32_merged_kernel, dim3(n_off + (unsigned)(nsplit_d * nb_all)), dim3(GR_THREADS), 0, c->stream, a, ad, n_off);
-        if (mid) RR_CHECK_HIP(hipEventRecord(mid, c->stream));
-        if (a.part)
-            hipLaunchKernelGGL(rr_syrk_det_reduce_kernel<float>, dim3((unsigned)((F + 1 + 255) / 256), (unsigned)F), dim3(256), 0,
-                               c->stream, a.part, a.part_stride, ldp, F, (int)nsplit, dG, bcol);
-        RR_CHECK_HIP(hipGetLastError());
-        return RR_OK;
-    }
-    if (ntiles > 0) {
-        if (syrk_mode == 1 && !a.ablate)
-            hipLaunchKernelGGL(rr_syrk_f32_flatstag_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(GR_THREADS), 0, c->stream, a);
-        else if (syrk_mode == 2 && !a.ablate)
-            hipLaunchKernelGGL(rr_syrk_f32_buf_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(GR_THREADS), 0, c->stream, a);
-        else if (syrk_mode == 0 || a.ablate)  // (the ablation switches live in the flat variant)
-            hipLaunchKernelGGL(rr_syrk_f32_flat_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(GR_THREADS), 0, c->stream, a);
-        else if (syrk_w8)
-            hipLaunchKernelGGL(rr_syrk_f32_w8_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(GR_THREADS), 0, c->stream, a);
-        else
-            hipLaunchKernelGGL(rr_syrk_f32_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(256), 0, c->stream, a);
-    }
-    if (rg) {
-        SyrkArgs ar = a;
-        ar.nb = nb_all;
-        ar.rows_per_split = rps_r;
-        hipLaunchKernelGGL(rr_syrk_f32_ragged_kernel, dim3((unsigned)(nsplit_r * (nb_all - 1))), dim3(GR_THREADS), 0, c->stream, ar);
+    if (pl.ragged.kernel) {
+        SyrkArgs ar = ad;
+        ar.rows_per_split = pl.ragged.rps;
+        hipLaunchKernelGGL(rr_syrk_f32_ragged_kernel, dim3((unsigned)pl.ragged.grid), dim3(GR_THREADS), 0, c->stream, ar);
     }
     if (mid) RR_CHECK_HIP(hipEventRecord(mid, c->stream));
-    if (od) {
-        SyrkArgs ad = a;
-        ad.nb = nb_all;
-        ad.rows_per_split = rps_d;
-        // diagonal blocks as 16x16 sub-blocks (round 3); RR_SYRK_NO_DIAG16=1: the whole-block kernel of round 2 (A/B runs)
-        static const bool no_diag16 = getenv("RR_SYRK_NO_DIAG16") != nullptr;
-        // RR_SYRK_DIAG_KB=64 (A/B runs): 64-row k-blocks when every K-split holds whole ones.  Measured in round 3 and not
-        // adopted: 87.7-88.1 vs 86.3-86.9 ms per 10M rows -- half the barriers buy nothing (DESIGN Appendix A.2)
-        static const bool kb64 = getenv("RR_SYRK_DIAG_KB") != nullptr && atoi(getenv("RR_SYRK_DIAG_KB")) == 64;
-        if (no_diag16)
-            hipLaunchKernelGGL(rr_syrk_f32_diag_kernel, dim3((unsigned)(nsplit_d * nb_all)), dim3(GR_THREADS), 0, c->stream, ad);
-        else if (kb64 && rows % 64 == 0 && ad.rows_per_split % 64 == 0)
-            hipLaunchKernelGGL(rr_syrk_f32_diag16_kernel<64>, dim3((unsigned)(nsplit_d * nb_all)), dim3(GR_THREADS), 0, c->stream, ad);
-        else
-            hipLaunchKernelGGL(rr_syrk_f32_diag16_kernel<32>, dim3((unsigned)(nsplit_d * nb_all)), dim3(GR_THREADS), 0, c->stream, ad);
+    switch (pl.diag.kernel) {  // (SK_F32_MERGED: went with the off-diagonal tiles)
+    case SK_F32_DIAG: hipLaunchKernelGGL(rr_syrk_f32_diag_kernel, g_diag, dim3(GR_THREADS), 0, c->stream, ad); break;
+    case SK_F32_DIAG16_64: hipLaunchKernelGGL(rr_syrk_f32_diag16_kernel<64>, g_diag, dim3(GR_THREADS), 0, c->stream, ad); break;
+    case SK_F32_DIAG16_32: hipLaunchKernelGGL(rr_syrk_f32_diag16_kernel<32>, g_diag, dim3(GR_THREADS), 0, c->stream, ad); break;
     }
-    if (a.part)
-        hipLaunchKernelGGL(rr_syrk_det_reduce_kernel<float>, dim3((unsigned)((F + 1 + 255) / 256), (unsigned)F), dim3(256), 0,
-                           c->stream, a.part, a.part_stride, ldp, F, (int)nsplit, dG, bcol);
+    syrk_det_reduce(c, pl, a.part, ldp, F, dG, bcol);
     RR_CHECK_HIP(hipGetLastError());
     return RR_OK;
 }
 
-int rr_launch_syrk_f64(rr_ctx *c, const double *P, int64_t rows, int64_t ldp, int F, double *dG, int lower_tri = 0) {
-    const int nb = (int)(ldp / G64_TC);
-    const int od = (nb >= 2 && !getenv("RR_SYRK_NO_DIAG_KERNEL")) ? 1 : 0;  // diagonal tiles in their own kernel
-    const int ntiles = od ? nb * (nb - 1) / 2 : nb * (nb + 1) / 2;
-    const int64_t slots = (int64_t)c->num_cu * 2;  // two workgroups per CU
-    // equal-cost workgroups: make their count a multiple of the slots (no partial last round) while a split keeps
-    // >= 2048 rows; otherwise ~4 rounds
-    int64_t g = slots, t = ntiles;
-    while (t) { const int64_t u = g % t; g = t; t = u; }
-    const int64_t unit = slots / g;
-    // (the posterior's C = Y^T Y at small F -- a square, triangular operand of <= 2048 rows: a few tiles whose k-loops are the
-    // whole launch -- splits down to 128 rows: at F = 1024 two splits of 512 rows left 56 workgroups walking up to 32
-    // k-blocks each, 69 + 40 us for a third of a GFLOP)
-    static const bool no_fine = getenv("RR_SYRK64_FINE_SPLIT") != nullptr && atoi(getenv("RR_SYRK64_FINE_SPLIT")) == 0;  // A/B runs
-    const int64_t min_rows = (lower_tri && rows == ldp && rows <= 2048 && !no_fine) ? 128 : 512;
-    int64_t nsplit = unit;
-    if (rows / nsplit < 2048) nsplit = (slots * 4 + ntiles - 1) / ntiles;
-    if (rows / nsplit < min_rows) nsplit = (rows + min_rows - 1) / min_rows;
-    if (nsplit < 1) nsplit = 1;
-    const int64_t rps = ((rows + nsplit - 1) / nsplit + G64_KB - 1) / G64_KB * G64_KB;
-    nsplit = (rows + rps - 1) / rps;
-    RR_REQUIRE(nsplit * ntiles < (int64_t)1 << 31, "gram: grid too large");
+int rr_launch_syrk_f64(rr_ctx *c, const double *P, int64_t rows, int64_t ldp, int F, double *dG, int lower_tri) {
+    const SyrkPlan pl = rr_plan_syrk_f64(rows, ldp, F, lower_tri, c->num_cu, c->deterministic, rr_syrk_switches());
+    if (pl.err) return rr_syrk_plan_status(pl);
     Syrk64Args a;
-    a.P = P; a.rows = rows; a.ldp = ldp; a.F = F; a.nb = nb; a.ntiles = ntiles; a.rows_per_split = rps; a.G = dG;
-    a.offdiag_only = od;
-    static const bool no_tri = getenv("RR_SYRK64_TRI") != nullptr && atoi(getenv("RR_SYRK64_TRI")) == 0;  // A/B runs
-    a.lower_tri = lower_tri && !no_tri && rows == ldp ? 1 : 0;
-    if (c->deterministic) {
-        void *slabs = nullptr;
-        int rc = rr_det_scratch(c, (size_t)nsplit * (size_t)ldp * (size_t)ldp * sizeof(double), &slabs);
-        if (rc != RR_OK) return rc;
-        a.part = (double *)slabs;
-        a.part_stride = ldp * ldp;
-    }
-    if (ntiles > 0)
-        hipLaunchKernelGGL(rr_syrk_f64_kernel, dim3((unsigned)(nsplit * ntiles)), dim3(G64_THREADS), 0, c->stream, a);
-    if (od) {
-        // the diagonal kernel's own K-split: nb equal-cost workgroups per split, up to 4 resident per CU (36 KiB of LDS
-        // each); pick the split count whose workgroup count fills whole rounds best while a split keeps >= 512 rows
-        const int64_t dslots = (int64_t)c->num_cu * 4;
-        int64_t best_ns = 1;
-        double best = -1.0;
-        for (int64_t ns = 1; ns <= 4 * dslots / nb + 1; ++ns) {
-            if (rows / ns < min_rows && ns > 1) break;
-            const int64_t wg = ns * nb, rounds = (wg + dslots - 1) / dslots;
-            const double eff = (double)wg / (double)(rounds * dslots);
-            if (eff > best + 1e-9) {
-                best = eff;
-                best_ns = ns;
-            }
-        }
+    a.P = P; a.rows = rows; a.ldp = ldp; a.F = F; a.nb = pl.nb; a.ntiles = pl.ntiles; a.rows_per_split = pl.off.rps; a.G = dG;
+    a.offdiag_only = pl.od;
+    a.lower_tri = pl.lower_tri;
+    int rc = syrk_det_slabs(c, pl, ldp, &a.part, &a.part_stride);
+    if (rc != RR_OK) return rc;
+    if (pl.off.kernel)
+        hipLaunchKernelGGL(rr_syrk_f64_kernel, dim3((unsigned)pl.off.grid), dim3(G64_THREADS), 0, c->stream, a);
+    if (pl.diag.kernel) {
         Syrk64Args ad = a;
-        ad.rows_per_split = ((rows + best_ns - 1) / best_ns + G64_KB - 1) / G64_KB * G64_KB;
-        if (c->deterministic) ad.rows_per_split = rps;  // one slab per K-split, shared by both kernels
-        const int64_t nsd = (rows + ad.rows_per_split - 1) / ad.rows_per_split;
-        hipLaunchKernelGGL(rr_syrk_f64_diag_kernel, dim3((unsigned)(nsd * nb)), dim3(G64_THREADS), 0, c->stream, ad);
+        ad.rows_per_split = pl.diag.rps;
+        hipLaunchKernelGGL(rr_syrk_f64_diag_kernel, dim3((unsigned)pl.diag.grid), dim3(G64_THREADS), 0, c->stream, ad);
     }
-    if (a.part)
-        hipLaunchKernelGGL(rr_syrk_det_reduce_kernel<double>, dim3((unsigned)((F + 255) / 256), (unsigned)F), dim3(256), 0,
-                           c->stream, a.part, a.part_stride, ldp, F, (int)nsplit, dG, (double *)nullptr);
+    syrk_det_reduce(c, pl, a.part, ldp, F, dG, (double *)nullptr);
     RR_CHECK_HIP(hipGetLastError());
     return RR_OK;
 }

@@ -298,21 +298,10 @@ int rr_launch_gemm_tn_bf16(rr_ctx *c, int nprod, const float *A, int64_t lda, co
 // producer (conversion path) falls back to the bf16 split with 3 products.
 int rr_launch_syrk_bf16(rr_ctx *c, int nprod, const float *P, const void *pb, int64_t rows, int64_t ldp, int F, double *dG,
                         hipEvent_t mid, float f16_scale) {
-    const int nb = (int)(ldp / GR_TC);
-    const int od = 0;
-    const int ntiles = nb * (nb + 1) / 2;
-    const int nxcd = 8;
-    const bool use_map = (ntiles % nxcd == 0) && !getenv("RR_GRAM_NO_TILE_MAP");
-    if (use_map && c->tile_map_nb != nb * 2 + od) {
-        std::vector<int> map;
-        rr_build_tile_map(nb, od, nxcd, map);
-        if (c->tile_map) (void)hipFree(c->tile_map);
-        c->tile_map = nullptr;
-        RR_CHECK_HIP(hipMalloc((void **)&c->tile_map, map.size() * sizeof(int)));
-        RR_CHECK_HIP(hipMemcpy(c->tile_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
-        c->tile_map_nb = nb * 2 + od;
-    }
-    const int64_t rows64 = (rows + 63) / 64 * 64;
+    const SyrkPlan pl = rr_plan_syrk_split16(rows, ldp, F, f16_scale > 0.f, c->num_cu, rr_syrk_switches());
+    int rc = pl.use_map ? rr_syrk_tile_map(c, pl.nb, pl.od) : RR_OK;
+    if (rc != RR_OK) return rc;
+    const int64_t rows64 = pl.rows;
     const size_t need = pb ? 0 : (size_t)rows64 * ldp * 4;
     if (c->pb_bytes < need) {
         RR_CHECK_HIP(hipStreamSynchronize(c->stream));
@@ -328,35 +317,14 @@ int rr_launch_syrk_bf16(rr_ctx *c, int nprod, const float *P, const void *pb, in
         pb = c->pb;
     }
     if (mid) RR_CHECK_HIP(hipEventRecord(mid, c->stream));
-    auto gcd64 = [](int64_t x, int64_t y) { while (y) { const int64_t u = x % y; x = y; y = u; } return x; };
-    // f32 accumulation per K-split: the fp16 engine is accurate enough (max error = the f32 engine's) for the pipe's
-    // accumulate bias to show in trace(G) -- 1.0e-6 of N at 32 768 rows per split, 6e-7 at 16 384 (+1.3 % time)
-    const int64_t max_rows_split = f16_scale > 0.f ? 16384 : 32768;
-    const int64_t min_splits = (rows64 + max_rows_split - 1) / max_rows_split;
-    const int64_t unit = c->num_cu / gcd64(c->num_cu, ntiles);
-    int64_t nsplit = (min_splits + unit - 1) / unit * unit;
-    if (rows64 / nsplit < 1024) nsplit = (rows64 + 1023) / 1024;
-    if (nsplit < 1) nsplit = 1;
-    int64_t rps = ((rows64 + nsplit - 1) / nsplit + 63) / 64 * 64;
-    const char *renv = getenv("RR_GRAM_ROWS_PER_SPLIT");
-    if (renv && atoll(renv) >= 64) rps = (atoll(renv) / 64) * 64;
-    else
-        while (rps > 64 && (rps / 16) * ldp * 64 + 32768 >= (int64_t)1 << 31) rps = (rps / 2 + 63) / 64 * 64;  // (see the check below)
-    nsplit = (rows64 + rps - 1) / rps;
-    RR_REQUIRE(nsplit * ntiles < (int64_t)1 << 31, "gram: grid too large");
-    // the kernel's LDS-DMA addresses a K-split's stages through ONE buffer descriptor with 32-bit offsets: stage g of the
-    // split sits g * ldp * 64 bytes behind its first (a wide matrix or a large RR_GRAM_ROWS_PER_SPLIT would wrap
-    // silently and the Gram would be wrong)
-    RR_REQUIRE((rps / 16) * ldp * 64 + 32768 < (int64_t)1 << 31,
-               "gram (split 16-bit engine): %lld rows per K-split of a %lld-column feature matrix exceed the kernel's 32-bit "
-               "stage offsets: lower RR_GRAM_ROWS_PER_SPLIT", (long long)rps, (long long)ldp);
+    if (pl.err) return rr_syrk_plan_status(pl);
     SyrkArgs a;
-    a.P = (const float *)pb; a.rows = rows64; a.ldp = ldp; a.F = F; a.nb = nb; a.ntiles = ntiles; a.rows_per_split = rps;
+    a.P = (const float *)pb; a.rows = rows64; a.ldp = ldp; a.F = F; a.nb = pl.nb; a.ntiles = pl.ntiles; a.rows_per_split = pl.off.rps;
     a.G = dG;
-    a.tile_map = use_map ? c->tile_map : nullptr;
-    a.offdiag_only = od;
-    a.ablate = getenv("RR_GRAM_ABLATE") ? atoi(getenv("RR_GRAM_ABLATE")) : 0;
-    const dim3 grid((unsigned)(nsplit * ntiles));
+    a.tile_map = pl.use_map ? c->tile_map : nullptr;
+    a.offdiag_only = pl.od;
+    a.ablate = pl.ablate;
+    const dim3 grid((unsigned)pl.off.grid);
     if (f16_scale > 0.f) {
         a.out_scale = 1.f / (f16_scale * f16_scale);
         hipLaunchKernelGGL((rr_syrk_b16w4_kernel<3, false, true>), grid, dim3(256), 0, c->stream, a);

@@ -92,8 +92,31 @@ __device__ __forceinline__ void rr_syrk_out(const SyrkArgs &p, int64_t ks, int64
 }
 #endif
 
-// Greedy XCD-aware tile order of the SYRK kernels (rr_rff.hip)
-void rr_build_tile_map(int nb, int od, int nxcd, std::vector<int> &map);
+// ---- the Gram launchers (plans, switches, tile map builder: rr_syrk_plan.h, included through rr_mfma_tile.h) ----
+// a failed plan's message into rr_last_error; returns its status
+inline int rr_syrk_plan_status(const SyrkPlan &pl) {
+    if (pl.err) rr_set_error("%s", pl.msg);
+    return pl.err;
+}
+// the context's XCD tile map for (nb, od), built and uploaded when the last Gram used another
+inline int rr_syrk_tile_map(rr_ctx *c, int nb, int od) {
+    if (c->tile_map_nb == nb * 2 + od) return RR_OK;
+    std::vector<int> map;
+    rr_build_tile_map(nb, od, SYRK_NXCD, map);
+    if (c->tile_map) (void)hipFree(c->tile_map);
+    c->tile_map = nullptr;
+    RR_CHECK_HIP(hipMalloc((void **)&c->tile_map, map.size() * sizeof(int)));
+    RR_CHECK_HIP(hipMemcpy(c->tile_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+    c->tile_map_nb = nb * 2 + od;
+    return RR_OK;
+}
+// rr_rff.hip
+// G(upper) += P^T P of a zero-padded f32 (rows % 32 == 0, ldp % 256 == 0) / f64 (rows % 16 == 0, ldp % 128 == 0) matrix.
+// mid: recorded between the off-diagonal and the diagonal kernels; bcol: Phi^T y from the rider column F;
+// lower_tri: P is square and lower triangular
+int rr_launch_syrk_f32(rr_ctx *c, const float *P, int64_t rows, int64_t ldp, int F, double *dG, hipEvent_t mid,
+                       double *bcol = nullptr);
+int rr_launch_syrk_f64(rr_ctx *c, const double *P, int64_t rows, int64_t ldp, int F, double *dG, int lower_tri = 0);
 
 // rr_syrk16.hip.  nprod: engine code (3, 4: bf16 products; 5: fp16x3 when f16_scale > 0, else bf16x3)
 int rr_launch_syrk_bf16(rr_ctx *c, int nprod, const float *P, const void *pb, int64_t rows, int64_t ldp, int F, double *dG,

@@ -54,7 +54,7 @@ SYRK_KERNELS = ["rr_syrk_f32_small_kernel", "rr_syrk_f32_kernel", "rr_syrk_f32_f
                 "rr_syrk_f32_buf_kernel", "rr_syrk_f32_ragged_kernel", "rr_syrk_f32_diag16_kernel", "rr_syrk_f32_diag_kernel",
                 "rr_syrk_f32_merged_kernel", "rr_syrk_det_reduce_kernel", "rr_syrk_b16w4_kernel", "rr_split_bf16_kernel",
                 "rr_syrk_f64_kernel", "rr_syrk_f64_diag_kernel", "rr_fm_set_column_kernel", "rr_fm_gemv_t_kernel"]
-# read once per process (static const in rr_launch_syrk_f32): each runs in a child process of its own
+# read once per process (rr_syrk_switches, rr_syrk_plan.h): each runs in a child process of its own
 AB_VARIANTS = [{"RR_SYRK_SMALL": "0"}, {"RR_SYRK_NO_DIAG16": "1"}, {"RR_SYRK_DIAG_KB": "64"}, {"RR_SYRK_MERGE_DIAG": "1"},
                {"RR_SYRK_STAGGER": "0"}, {"RR_SYRK_STAGGER": "1"}, {"RR_SYRK_STAGGER": "2"}, {"RR_SYRK_SPLIT_SEARCH": "0"}]
 AB_NAMES = sorted({k for v in AB_VARIANTS for k in v})
