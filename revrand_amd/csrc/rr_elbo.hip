@@ -13,13 +13,9 @@
 #include "rr_internal.h"
 #include "rr_mfma_tile.h"
 #include "rr_syrk_args.h"  // rr_launch_syrk_f64
-#include <atomic>
+#include "rr_workers.h"
 #include <chrono>
-#include <condition_variable>
 #include <functional>
-#include <mutex>
-#include <thread>
-#include <unistd.h>
 
 // ---------------------------------------------------------------------------------------------
 // Feature-major features:  Pt[f][r] = cos/sqrt(n), Pt[n+f][r] = sin/sqrt(n)  (GEMM operand, K-major),
@@ -3265,107 +3261,46 @@ static inline int64_t sgd_now_ns() {
     return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// The members of a device group are queued CONCURRENTLY: member 0 on the calling thread, member i > 0 on worker i of this
-// pool -- a part of a step is ~10-15 launches per member (~150 us of host time per step and member), which one thread
-// queueing 8 members in turn would stretch to more than the members' kernels take.  A context is still served by one thread at
-// a time (the caller waits for all workers before it goes on); a worker's error text is handed back to the caller's thread.
-// Workers spin for a millisecond after a job (the next part of the step is tens of microseconds away), then sleep.
-class SgdGroupWorkers {
-  public:
-    static SgdGroupWorkers &get() {
-        static SgdGroupWorkers *pool = nullptr;
-        static std::mutex mu;
-        std::lock_guard<std::mutex> lk(mu);
-        if (!pool || pool->pid_ != getpid()) pool = new SgdGroupWorkers();  // (a fork's inheritance is abandoned, not joined)
-        return *pool;
-    }
-    // fn(i) for i in [0, n); the first failure's status (its message restored on this thread)
-    int run(int n, const std::function<int(int)> &fn) {
-        static const bool serial = [] { const char *e = getenv("RR_GLM_GROUP_THREADS"); return e && atoi(e) == 0; }();
-        if (n <= 1 || serial) {
-            for (int i = 0; i < n; ++i) {
-                const int rc = fn(i);
-                if (rc != RR_OK) return rc;
-            }
-            return RR_OK;
+// The members of a device group are queued CONCURRENTLY: member 0 on the calling thread, member i > 0 on worker i - 1 of the
+// group's pool (rr_workers.h) -- a part of a step is ~10-15 launches per member (~150 us of host time per step and member),
+// which one thread queueing 8 members in turn would stretch to more than the members' kernels take.  A context is still
+// served by one thread at a time (the caller waits for all workers before it goes on).  Workers spin for a millisecond
+// after a job (the next part of the step is tens of microseconds away), then sleep; the caller yields 65536 times first.
+static ProcessWorkerPool sgd_group_workers(1000, 1 << 16);
+
+// fn(i) for i in [0, n): member 0's status if it failed, else the first failing member's in member order, with that
+// member's error text restored on this thread.  RR_GLM_GROUP_THREADS=0 (read once): one after the other on this thread.
+static int sgd_group_run(int n, const std::function<int(int)> &fn) {
+    static const bool serial = [] { const char *e = getenv("RR_GLM_GROUP_THREADS"); return e && atoi(e) == 0; }();
+    if (n <= 1 || serial) {
+        for (int i = 0; i < n; ++i) {
+            const int rc = fn(i);
+            if (rc != RR_OK) return rc;
         }
-        std::lock_guard<std::mutex> one(call_);
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            while ((int)slots_.size() < n - 1) {
-                slots_.emplace_back(new Slot());
-                const int id = (int)slots_.size() - 1;
-                std::thread([this, id] { loop(id); }).detach();
-            }
-            job_ = &fn;
-            want_ = n - 1;
-            remaining_.store(n - 1, std::memory_order_relaxed);
-            gen_.fetch_add(1, std::memory_order_release);
-        }
-        cv_.notify_all();
-        int rc = fn(0);
-        for (int spin = 0; remaining_.load(std::memory_order_acquire) > 0; ++spin) {
-            if (spin < 1 << 16) std::this_thread::yield();
-            else {
-                std::unique_lock<std::mutex> lk(mu_);
-                done_.wait_for(lk, std::chrono::microseconds(200), [this] { return remaining_.load(std::memory_order_acquire) == 0; });
-            }
-        }
-        if (rc != RR_OK) return rc;
-        for (int i = 0; i < n - 1; ++i)
-            if (slots_[(size_t)i]->rc != RR_OK) {
-                rr_set_error("%s", slots_[(size_t)i]->err.c_str());
-                return slots_[(size_t)i]->rc;
-            }
         return RR_OK;
     }
-
-  private:
     struct Slot {
         int rc = RR_OK;
         std::string err;
     };
-    SgdGroupWorkers() : pid_(getpid()) {}
-    void loop(int id) {
-        int64_t seen = 0;
-        for (;;) {
-            int64_t g = gen_.load(std::memory_order_acquire);
-            const auto t0 = std::chrono::steady_clock::now();
-            while (g == seen) {
-                std::this_thread::yield();
-                g = gen_.load(std::memory_order_acquire);
-                if (g == seen && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(1000)) {
-                    std::unique_lock<std::mutex> lk(mu_);
-                    cv_.wait(lk, [&] { return gen_.load(std::memory_order_acquire) != seen; });
-                    g = gen_.load(std::memory_order_acquire);
-                }
-            }
-            seen = g;
-            const std::function<int(int)> *fn;
-            Slot *slot;
-            {
-                std::lock_guard<std::mutex> lk(mu_);
-                if (id >= want_) continue;
-                fn = job_;
-                slot = slots_[(size_t)id].get();
-            }
-            slot->rc = (*fn)(id + 1);
-            if (slot->rc != RR_OK) slot->err = rr_last_error();
-            if (remaining_.fetch_sub(1, std::memory_order_acq_rel) == 1) {
-                std::lock_guard<std::mutex> lk(mu_);
-                done_.notify_all();
-            }
+    std::vector<Slot> slots((size_t)n - 1);
+    auto member = [&](int id) {
+        Slot &s = slots[(size_t)id];
+        s.rc = fn(id + 1);
+        if (s.rc != RR_OK) s.err = rr_last_error();
+    };
+    WorkerPool &pool = sgd_group_workers.get();
+    pool.start(n - 1, member);
+    const int rc = fn(0);
+    pool.wait();
+    if (rc != RR_OK) return rc;
+    for (const Slot &s : slots)
+        if (s.rc != RR_OK) {
+            rr_set_error("%s", s.err.c_str());
+            return s.rc;
         }
-    }
-    pid_t pid_;
-    std::mutex mu_, call_;
-    std::condition_variable cv_, done_;
-    std::vector<std::unique_ptr<Slot>> slots_;
-    const std::function<int(int)> *job_ = nullptr;
-    int want_ = 0;
-    std::atomic<int> remaining_{0};
-    std::atomic<int64_t> gen_{0};
-};
+    return RR_OK;
+}
 
 __global__ void __launch_bounds__(256)
 rr_glm_sgd_from_log_kernel(const double *__restrict__ z, const unsigned char *__restrict__ islog, int64_t np, double *__restrict__ x) {
@@ -4106,15 +4041,14 @@ int rr_glm_sgd_group_step(int n, rr_glm_sgd *const *loops, rr_comm *const *comms
     std::vector<double *> bufs((size_t)n);
     static const bool timing = getenv("RR_GLM_GROUP_TIMING") != nullptr;
     const int64_t t_call = timing ? sgd_now_ns() : 0;
-    SgdGroupWorkers &pool = SgdGroupWorkers::get();
-    int rc = pool.run(n, [&](int i) { return sgd_step_front(loops[i], in[(size_t)i]); });
+    int rc = sgd_group_run(n, [&](int i) { return sgd_step_front(loops[i], in[(size_t)i]); });
     if (rc != RR_OK) return rc;
     if (o0->n_ls) {
         for (int i = 0; i < n; ++i) bufs[(size_t)i] = loops[i]->dT;
         rc = rr_comm_group_allreduce_dev(comms, n, bufs.data(), o0->dT_count, RR_COMM_SUM);
         if (rc != RR_OK) return rc;
     }
-    rc = pool.run(n, [&](int i) { return sgd_step_middle(loops[i], in[(size_t)i]); });
+    rc = sgd_group_run(n, [&](int i) { return sgd_step_middle(loops[i], in[(size_t)i]); });
     if (rc != RR_OK) return rc;
     // [Edm | EdC] and [llsum | aux]: one run of 2 F K + 2 K doubles when the scratch was made for this K (fm_glm_scratch), else two
     const int kcap = ((FmPass2 *)sgd_step_fm(o0)->pass2)->kcap;
@@ -4131,7 +4065,7 @@ int rr_glm_sgd_group_step(int n, rr_glm_sgd *const *loops, rr_comm *const *comms
         for (int i = 0; i < n; ++i) bufs[(size_t)i] = ((FmPass2 *)sgd_step_fm(loops[i])->pass2)->kacc;
         rc = rr_comm_group_allreduce_dev(comms, n, bufs.data(), 2 * (int64_t)kcap, RR_COMM_SUM);
     }
-    if (rc == RR_OK) rc = pool.run(n, [&](int i) { return sgd_step_back(loops[i], in[(size_t)i]); });
+    if (rc == RR_OK) rc = sgd_group_run(n, [&](int i) { return sgd_step_back(loops[i], in[(size_t)i]); });
     if (timing) {
         o0->call_ns += sgd_now_ns() - t_call;
         o0->group_steps += 1;
