@@ -313,7 +313,8 @@ int rr_featmat_glm_centres(rr_featmat *fm, rr_basis *basis, const void *dX, int 
  * Same protocol as rr_featmat_*: begin(rows); every child puts its column block (random Fourier children are evaluated in
  * float64 whatever their own arithmetic); gram accumulates into DEVICE f64 buffers; pass2_begin(m, C) -> pass2_rows(dy) ->
  * pass2_rff per random Fourier child -> pass2_end(&sqErr), or pass2_begin -> predict_rows(Ey, Vf).  C: host (F, F) or,
- * with c_on_device != 0, a device pointer (rr_posterior_dev's output).  No GLM step, no split engines. */
+ * with c_on_device != 0, a device pointer (rr_posterior_dev's output).  The GLM step on this matrix is rr_featmat64_glm_*
+ * below.  No split engines. */
 typedef struct rr_featmat64 rr_featmat64;
 int rr_featmat64_create(rr_ctx *ctx, int64_t max_rows, int64_t F, rr_featmat64 **out);
 void rr_featmat64_destroy(rr_featmat64 *fm);
@@ -342,6 +343,40 @@ int rr_featmat64_put_poly(rr_featmat64 *fm, const void *dX, int x_dtype, int64_t
                           int64_t col0);
 int rr_featmat64_pass2_centres(rr_featmat64 *fm, rr_basis *basis, const void *dX, int x_dtype, int64_t ldx, int64_t col0,
                                double *dg);
+/* ---- the GLM SVI step on the float64 matrix (GeneralizedLinearModel(dtype="f64"); rr_glm64.hip) ----------------------------
+ * rr_featmat_glm_step / _step_draws / _glm_rff / _glm_centres / _glm_edphi / _project with every product and sum in float64:
+ * three f64 MFMA products (fs = P WS^T, Ed = dfs^T P, EdPhi = dfs WS), the likelihood terms in float64 (accurate softplus and
+ * expit, the division-free softplus-link Poisson), all sums in a fixed order -- no floating-point atomics, the same bits every
+ * run in either determinism mode.  Outputs mean what their rr_featmat_* namesakes' mean (Gaussian: aux = sum (y - f)^2, llsum =
+ * -aux / (2 var); the f-independent constants stay with the host).  dy / drowarg: device float32 or float64 (dtype).
+ *   glm_step        the caller's weight samples WS, host float64 (K L, F) -> Edws (K L, F), llsum (K), aux (K)
+ *   glm_step_draws  E: host FLOAT64 (K L, F) standard normals, component-major; ws = m_k + sqrt(C_k) e on the device (m, C host
+ *                   (F, K)); Edm, EdC host (K, F).  Edm == EdC == NULL: objective only -- fs and the likelihood sums, none of
+ *                   the gradient products
+ *   glm_rff         dT (d, n) += X^T (E_s o P_c - E_c o P_s) from the stored EdPhi, Xdim <= 128 as rr_featmat64_pass2_rff
+ *   glm_centres     the length scales' contraction of rr_featmat64_pass2_centres against EdPhi (two fixed-order stages; the
+ *                   (basis, col0) must have been put)
+ *   glm_edphi       EdPhi[:, col0 : col0 + ncols] to host float64 (rows, ncols), for children whose gradient is formed on the host
+ *   project         out (rows, S) = P W, W host float64 (F, S)
+ * EdPhi lives in the second pass' U: rr_featmat64_begin and rr_featmat64_pass2_begin / _rows / _predict_rows invalidate it, a step (or project)
+ * invalidates the second pass' rows -- glm_rff / glm_centres / glm_edphi without a step since, or pass2_rff / pass2_centres
+ * after one, are refused.  Refused before any launch (RR_ERR_INVALID): an incomplete matrix, a binomial without drowarg, a
+ * variance <= 0, K L >= 2^24, an empty matrix, a child that was not put.
+ * rr_glm64_plan (host only, no device): how the Ed product's k-loop over the rows is cut for (rows, F, K L) on num_cu compute
+ * units -- out = {row slabs, slab length (a multiple of 16), output tiles, rows_pad}.  One slab when the tiles alone are at
+ * least 2 num_cu; else the smallest count with tiles x slabs >= num_cu, at most rows_pad / 128, moved up to the next count whose
+ * equal slabs leave the last one non-empty.  The step asks the same function (RR_GLM64_KSLABS=<n> forces the count: A/B runs). */
+int rr_glm64_plan(int64_t rows, int64_t F, int KL, int num_cu, int64_t out[4]);
+int rr_featmat64_glm_step(rr_featmat64 *fm, const void *dy, const void *drowarg, int dtype, int lik, double lik_param,
+                          const double *WS, int K, int L, double *Edws, double *llsum, double *aux);
+int rr_featmat64_glm_step_draws(rr_featmat64 *fm, const void *dy, const void *drowarg, int dtype, int lik, double lik_param,
+                                const double *m, const double *C, int K, int L, const double *E, double *Edm, double *EdC,
+                                double *llsum, double *aux);
+int rr_featmat64_glm_rff(rr_featmat64 *fm, rr_basis *basis, const void *dX, int x_dtype, int64_t ldx, int64_t col0, double *dT);
+int rr_featmat64_glm_centres(rr_featmat64 *fm, rr_basis *basis, const void *dX, int x_dtype, int64_t ldx, int64_t col0,
+                             double *dg);
+int rr_featmat64_glm_edphi(rr_featmat64 *fm, int64_t col0, int64_t ncols, double *E);
+int rr_featmat64_project(rr_featmat64 *fm, const double *W, int S, double *out);
 /* The rows of the current rr_featmat64_begin as they sit in HBM: out host float64 (rows, ld), ld = F rounded up to a multiple
  * of 128, padding columns included.  For tests and diagnostics. */
 int rr_featmat64_download(rr_featmat64 *fm, double *out);

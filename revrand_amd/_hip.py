@@ -138,6 +138,20 @@ SIGNATURES = {
     "rr_featmat64_pass2_centres": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "rr_featmat64_download": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "rr_glm64_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "rr_featmat64_glm_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rr_featmat64_glm_step_draws": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rr_featmat64_glm_rff": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "rr_featmat64_glm_centres": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "rr_featmat64_glm_edphi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "rr_featmat64_project": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "rr_rff_elbo_pass2_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -1474,7 +1488,8 @@ def svi_supported_gm(F, K, L, M, n_children, dsum, n_ls, table_entries):
 
 class FeatureMatrix64(object):
     """The float64 device feature matrix of a concatenated basis (rr_featmat64): the subset of FeatureMatrix a resident fit
-    needs -- children put column blocks, Gram, second pass, prediction -- in the reference's arithmetic."""
+    needs -- children put column blocks, Gram, second pass, prediction -- and the GLM SVI step (glm_step, glm_step_draws, the
+    children's contractions, project) in the reference's arithmetic."""
 
     dtype = np.dtype(np.float64)
 
@@ -1567,6 +1582,70 @@ class FeatureMatrix64(object):
         _check(self.lib, self.lib.rr_featmat64_predict_rows(self.h, Ey.ctypes.data_as(ctypes.c_void_p),
                                                             Vf.ctypes.data_as(ctypes.c_void_p)))
         return Ey, Vf
+
+    # -- the GLM SVI step in float64 (rr_glm64.hip); argument order as FeatureMatrix' namesakes --------------------------
+    def glm_step(self, dy, drowarg, lik, lik_param, WS, K, L):
+        """(Edws (K*L, F), llsum (K,), aux (K,)) of one SVI minibatch step in float64 (rr_featmat64_glm_step)."""
+        WS = np.ascontiguousarray(WS, dtype=np.float64)
+        if WS.shape != (K * L, self.F):
+            raise ValueError("weight samples must have shape (K*L, F)")
+        Edws, ll, aux = np.empty((K * L, self.F)), np.empty(K), np.empty(K)
+        _check(self.lib, self.lib.rr_featmat64_glm_step(self.h, _ptr(dy), _ptr(drowarg), rr_dtype(dy.dtype), int(lik),
+                                                        float(lik_param), WS.ctypes.data_as(ctypes.c_void_p), K, L,
+                                                        Edws.ctypes.data_as(ctypes.c_void_p),
+                                                        ll.ctypes.data_as(ctypes.c_void_p),
+                                                        aux.ctypes.data_as(ctypes.c_void_p)))
+        return Edws, ll, aux
+
+    def glm_step_draws(self, dy, drowarg, lik, lik_param, m, C, K, L, E, objective_only=False):
+        """(Edm (F, K), EdC (F, K), llsum, aux) for the caller's standard-normal draws E, host float64 (K*L, F);
+        objective_only: (None, None, llsum, aux) without the gradient products."""
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        C = np.ascontiguousarray(C, dtype=np.float64)
+        if isinstance(E, DeviceBuffer):
+            raise TypeError("the float64 step takes its draws from the host (float64); device-resident draws are float32")
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        if m.shape != (self.F, K) or C.shape != (self.F, K) or E.shape != (K * L, self.F):
+            raise ValueError("m, C must have shape (F, K) and E (K*L, F)")
+        Edm, EdC, ll, aux = np.empty((K, self.F)), np.empty((K, self.F)), np.empty(K), np.empty(K)
+        none = ctypes.c_void_p(None)
+        _check(self.lib, self.lib.rr_featmat64_glm_step_draws(
+            self.h, _ptr(dy), _ptr(drowarg), rr_dtype(dy.dtype), int(lik), float(lik_param),
+            m.ctypes.data_as(ctypes.c_void_p), C.ctypes.data_as(ctypes.c_void_p), K, L, E.ctypes.data_as(ctypes.c_void_p),
+            none if objective_only else Edm.ctypes.data_as(ctypes.c_void_p),
+            none if objective_only else EdC.ctypes.data_as(ctypes.c_void_p), ll.ctypes.data_as(ctypes.c_void_p),
+            aux.ctypes.data_as(ctypes.c_void_p)))
+        return (None, None, ll, aux) if objective_only else (Edm.T, EdC.T, ll, aux)
+
+    def glm_rff(self, handle, dX, col0, dT):
+        _check(self.lib, self.lib.rr_featmat64_glm_rff(self.h, handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, col0, _ptr(dT)))
+
+    def glm_centres(self, handle, dX, col0, dg):
+        """dg += sum(EdPhi o dPhi_i) per length scale of a centres child, after a GLM step, in float64."""
+        _check(self.lib, self.lib.rr_featmat64_glm_centres(self.h, handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, col0, _ptr(dg)))
+
+    def glm_edphi(self, rows, col0, ncols):
+        E = np.empty((rows, ncols))
+        _check(self.lib, self.lib.rr_featmat64_glm_edphi(self.h, col0, ncols, E.ctypes.data_as(ctypes.c_void_p)))
+        return E
+
+    def project(self, rows, W):
+        """(rows, S) = P W for a host (F, S) matrix, in float64 (rr_featmat64_project)."""
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[0] != self.F:
+            raise ValueError("W must have shape (F, S)")
+        out = np.empty((rows, W.shape[1]))
+        _check(self.lib, self.lib.rr_featmat64_project(self.h, W.ctypes.data_as(ctypes.c_void_p), W.shape[1],
+                                                       out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+
+def glm64_plan(rows, F, KL, num_cu):
+    """(row slabs, slab length, output tiles, rows_pad) of the float64 GLM step's Ed product (rr_glm64_plan; needs no device)."""
+    out = (ctypes.c_int64 * 4)()
+    lib = load_library()
+    _check(lib, lib.rr_glm64_plan(int(rows), int(F), int(KL), int(num_cu), out))
+    return tuple(int(v) for v in out)
 
 
 def hadamard(Y, ordering=True, device=None):

@@ -448,11 +448,12 @@ class _ResidentRFF(object):
 
     nparams = 1
 
-    def __init__(self, basis, X):
+    def __init__(self, basis, X, x_dtype=None):
         self.basis = basis
         self.h, W = basis._dense_handle()
         self.W = np.asarray(W, dtype=np.float64)
-        self.dX = self.h.upload(np.ascontiguousarray(X, dtype=self.h.x_dtype))
+        # x_dtype: what the rows are kept in when not the handle's own (the float64 GLM step keeps float64 rows for f32 bases too)
+        self.dX = self.h.upload(np.ascontiguousarray(X, dtype=self.h.x_dtype if x_dtype is None else x_dtype))
         self.dT = self.h.dev.zeros(self.W.size * 8)
 
     def put(self, fm, X, r0, rows, col0, params):
@@ -592,8 +593,8 @@ class _ResidentCentres(object):
     scales' gradient contracted on the device against the second pass' (or the GLM step's) scratch into `dg` -- one float64
     per length scale, summed in a fixed order (rr_featmat_pass2_centres / rr_featmat_glm_centres).  dtype="f64": the child of a
     float64 state (FeatureMatrix64: rr_featmat64_put_centres / rr_featmat64_pass2_centres) -- X resident as float64, every
-    product in float64 whatever the basis' own dtype; that state has no GLM step, so `gather`, `put_batch` and `glm_grad` are
-    the f32 mode's alone."""
+    product in float64 whatever the basis' own dtype; `gather`, `put_batch` and `glm_grad` serve the float64 GLM step
+    (MinibatchFeatures64: rr_featmat64_glm_centres) through the same calls."""
 
     nparams = 1
 
@@ -753,7 +754,8 @@ class MinibatchFeatures(object):
         """Upload the step's targets (and per-row likelihood argument) BEFORE its features are launched: the copies
         synchronise the stream, and behind the feature kernels they would make the host wait for them."""
         self._targets = None
-        staged = (self._stage("y", y, np.float32), None if rowarg is None else self._stage("rowarg", rowarg, np.float32))
+        td = self._target_dtype
+        staged = (self._stage("y", y, td), None if rowarg is None else self._stage("rowarg", rowarg, td))
         self._targets = (id(y), len(y), rowarg is None) + staged
 
     def _take_targets(self, y, rowarg):
@@ -762,7 +764,10 @@ class MinibatchFeatures(object):
         t, self._targets = self._targets, None
         if t is not None and t[:3] == (id(y), len(y), rowarg is None):
             return t[3], t[4]
-        return self._stage("y", y, np.float32), None if rowarg is None else self._stage("rowarg", rowarg, np.float32)
+        td = self._target_dtype
+        return self._stage("y", y, td), None if rowarg is None else self._stage("rowarg", rowarg, td)
+
+    _target_dtype = np.float32  # what y and the per-row likelihood argument are staged as (MinibatchFeatures64: float64)
 
     def _ensure(self, rows, F):
         if self.fm is None or self.fm.max_rows < rows or self.fm.F != F:
@@ -988,6 +993,89 @@ class MinibatchFeatures(object):
         self.fm = None
 
 
+class MinibatchFeatures64(MinibatchFeatures):
+    """MinibatchFeatures on the FLOAT64 feature matrix (GeneralizedLinearModel(dtype="f64"); rr_glm64.hip): the same
+    ``assemble`` / ``assemble_idx`` / ``glm_step`` / ``glm_step_draws`` / ``glm_basis_grads`` / ``project``, every product and sum of
+    the step in float64, ``y`` and the per-row likelihood argument staged as float64 (counts above 2^24 stay exact), the draws
+    taken as host float64.  The children are the float64 states' (``_resident_child(X, dtype="f64", ...)``, as BasisCat's float64
+    fit state asks): random Fourier children of Xdim <= 128 (their rows resident as float64 whatever the basis' own dtype) and
+    LinearBasis on the device; under resident_bases="all" RadialBasis / SigmoidalBasis / PolynomialBasis too; every other basis
+    (FastFoodRBF, FastFoodGM, wide inputs) through its own ``transform`` and ``put_host``, its gradient from the downloaded EdPhi
+    block and ``basis.grad`` on the host.  ``make_resident`` works when every child can gather float64 rows; otherwise the rows
+    come from the host per step.  No device sampler, no device-resident draws, no ``predictive``."""
+
+    _target_dtype = np.float64
+    accepts_device_draws = False
+
+    def __init__(self, basis, resident_bases="fourier"):
+        super().__init__(basis)
+        self.resident_bases = resident_bases
+
+    def _ensure(self, rows, F):
+        if self.fm is None or self.fm.max_rows < rows or self.fm.F != F:
+            self.fm = None  # free the old one first
+            self.fm = _hip.FeatureMatrix64(rows, F)
+            self.dev = self.fm.dev
+
+    def _child(self, b, X):
+        every = self.resident_bases == "all"
+        if getattr(b, "_child_options", False):
+            c = b._resident_child(X, dtype="f64", f64_children=every, wide=every)
+        elif getattr(b, "_rows64_option", False):
+            # an f32 random Fourier basis keeps its rows as float32 in a float64 Gram state; the GLM step's rows are float64
+            c = b._resident_child(X, dtype="f64", rows64=True)
+        else:
+            c = b._resident_child(X, dtype="f64")
+        return c
+
+    def make_resident(self, X, resident_bases=None, dense_gm=False):
+        if resident_bases is not None:
+            self.resident_bases = resident_bases
+        self._drop_children()
+        kids = []
+        for b in self.bases:
+            c = self._child(b, X)
+            if c is None or not hasattr(c, "gather"):
+                for k in kids + ([c] if c is not None else []):
+                    k.release()
+                return False
+            kids.append(c)
+        self._kids = kids
+        self._dims = [int(b.get_dim(X)) for b in self.bases]
+        self.resident = True
+        return True
+
+    def prefetch_batch(self, updev, idx, y, rowarg):
+        raise TypeError("the float64 GLM features have no look-ahead stage")
+
+    def assemble(self, X, hypers):
+        self._targets = None
+        self._drop_children()
+        M = X.shape[0]
+        dims = [int(b.get_dim(X)) for b in self.bases]
+        self._ensure(M, int(sum(dims)))
+        self.fm.begin(M)
+        args, col0 = list(hypers), 0
+        for b, w in zip(self.bases, dims):
+            child = self._child(b, X)
+            if child is None:
+                child = _ResidentGeneric(b)
+            mine, args = args[:child.nparams], args[child.nparams:]
+            child.put(self.fm, X, 0, M, col0, mine)
+            self.children.append((child, col0, w))
+            col0 += w
+        self.M = M
+
+    def _plan_basis_grads(self, objective_only=False):
+        self._planned = False   # (the float64 step always stores EdPhi; glm_rff contracts it)
+
+    def glm_step_sampled(self, *args, **kwargs):
+        raise TypeError("the float64 GLM step has no device sampler")
+
+    def predictive(self, *args, **kwargs):
+        raise TypeError("predict_engine='device' is not offered on the float64 feature matrix")
+
+
 class _Gathered(object):
     """A minibatch made ready on the device ahead of its step (MinibatchFeatures.prefetch_batch)."""
 
@@ -1202,11 +1290,14 @@ class _RandomKernelBasis(_LengthScaleBasis):
         return self._handle(), self.W
 
     @slice_transform
-    def _resident_child(self, X, dtype=None):
-        # float64 bases join a float64 state only; f32 bases join either (a float64 feature matrix evaluates them in float64)
+    def _resident_child(self, X, dtype=None, rows64=False):
+        # float64 bases join a float64 state only; f32 bases join either (a float64 feature matrix evaluates them in float64);
+        # rows64 (MinibatchFeatures64): the rows resident as float64 whatever the basis' own dtype
         if (self.dtype != "f32" and dtype != "f64") or X.shape[1] != self.d or (dtype == "f64" and self.d > 128):
             return None
-        return _ResidentRFF(self, X)
+        return _ResidentRFF(self, X, np.float64 if rows64 else None)
+
+    _rows64_option = True  # `_resident_child` takes rows64
 
     _predict_checks_rows = True  # `predict_moments` runs the caller's row validation itself (chunk by chunk, under the GPU's work)
 

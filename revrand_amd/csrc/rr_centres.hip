@@ -490,7 +490,8 @@ rr_centres_features64_wide_kernel(const TX *__restrict__ X, int64_t rows, int64_
 // (i, slice) as there; every product and sum is float64, added in a fixed order: per thread over its units and the block's
 // rows, across the slices in slice order, the block's nd sums to partial[block][i] (then rr_det_reduce).  No atomics.
 // LDS (all dynamic): centres [16][DP] double2, w [RT64][CT64], rows [RT64][DP + 1], the slices' sums [256].
-template <typename TX, int KIND>
+// SLM = false (the float64 GLM step, rr_featmat64_glm_centres): E = U, the step's EdPhi; err and mvec are not read.
+template <typename TX, int KIND, bool SLM = true>
 __global__ void __launch_bounds__(256)
 rr_centres_contract64_kernel(const TX *__restrict__ X, int64_t rows, int64_t ldx, int nd, int DP, const double *__restrict__ Ct, int Mp,
                              int M, const double *__restrict__ P, const double *__restrict__ U, int64_t ldp,
@@ -526,7 +527,7 @@ rr_centres_contract64_kernel(const TX *__restrict__ X, int64_t rows, int64_t ldx
             if (n < rb1 && j < M) {
                 RR_DEV_ASSERT(j < ldp);
                 const double phi = P[n * ldp + j], u = U[n * ldp + j];
-                const double E = fma(err[n], mvec[j], -u);
+                const double E = SLM ? fma(err[n], mvec[j], -u) : u;
                 w = KIND == RR_CENTRES_RADIAL ? E * phi : -E * phi * (1.0 - phi);
             }
             ws[e] = w;
@@ -1076,11 +1077,16 @@ int rr_featmat64_put_poly(rr_featmat64 *fm, const void *dX, int x_dtype, int64_t
     return RR_OK;
 }
 
-int rr_featmat64_pass2_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, double *dg) {
-    const char *who = "rr_featmat64_pass2_centres";
+extern "C++" {
+// SLM: the second pass' E = Err m^T - Phi C (after rr_featmat64_pass2_rows); else the GLM step's E = EdPhi (after a step that
+// stored it, rr_glm64.hip) -- one launcher, as centres_contract<SLM> is for the f32 matrix
+template <bool SLM>
+static int centres_contract64(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, double *dg,
+                              const char *who) {
     CentresData *cd = centres_of(b);
     RR_REQUIRE(fm != nullptr && cd != nullptr && dg != nullptr, "%s: bad argument", who);
-    RR_REQUIRE(fm->Pt != nullptr && fm->have_rows, "%s: call rr_featmat64_pass2_rows first", who);
+    if (SLM) RR_REQUIRE(fm->Pt != nullptr && fm->have_rows, "%s: call rr_featmat64_pass2_rows first", who);
+    else RR_REQUIRE(fm->U != nullptr && fm->have_edphi, "%s: call rr_featmat64_glm_step first", who);
     RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "%s: bad dtype", who);
     RR_REQUIRE(b->d <= RR_CENTRES_MAX_DIM, "%s: needs d <= %d, got %d", who, RR_CENTRES_MAX_DIM, b->d);
     RR_REQUIRE(col0 >= 0 && col0 + (int64_t)cd->M <= fm->F, "%s: columns out of range", who);
@@ -1117,7 +1123,7 @@ int rr_featmat64_pass2_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, in
         const size_t lds = ((size_t)2 * 16 * DP + (size_t)RT64 * CT64 + (size_t)RT64 * (DP + 1) + 256) * 8;
         const double *Ct = cd->Ct64 + (size_t)i0 * cd->Mp;
 #define RR_CC64(TX, KIND)                                                                                                      \
-        hipLaunchKernelGGL((rr_centres_contract64_kernel<TX, KIND>), grid, dim3(256), lds, c->stream, (const TX *)dX + i0, fm->rows, ldx, \
+        hipLaunchKernelGGL((rr_centres_contract64_kernel<TX, KIND, SLM>), grid, dim3(256), lds, c->stream, (const TX *)dX + i0, fm->rows, ldx, \
                            nd, DP, Ct, cd->Mp, cd->M, P, Uc, fm->ld, fm->err, mv, gfac, (int)rpb, (double *)part)
         if (cd->kind == RR_CENTRES_RADIAL) {
             if (x_dtype == RR_F32) RR_CC64(float, RR_CENTRES_RADIAL);
@@ -1132,6 +1138,15 @@ int rr_featmat64_pass2_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, in
         if (rc != RR_OK) return rc;
     }
     return RR_OK;
+}
+}  // extern "C++"
+
+int rr_featmat64_pass2_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, double *dg) {
+    return centres_contract64<true>(fm, b, dX, x_dtype, ldx, col0, dg, "rr_featmat64_pass2_centres");
+}
+
+int rr_featmat64_glm_centres(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, int64_t col0, double *dg) {
+    return centres_contract64<false>(fm, b, dX, x_dtype, ldx, col0, dg, "rr_featmat64_glm_centres");
 }
 
 int rr_featmat64_download(rr_featmat64 *fm, double *out) {

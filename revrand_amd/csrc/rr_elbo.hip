@@ -1864,6 +1864,16 @@ rr_transpose_f64_kernel(const double *__restrict__ P, int64_t rows, int64_t ldp,
     for (int k = 0; k < 16; ++k) Pt[(c0 + ty + 4 * k) * ldt + r0 + tx] = tile[tx][ty + 4 * k];
 }
 
+// Pt (cols_pad, ldt) = P^T over rows_pad rows (both multiples of 64; rows >= `rows` as zeros), for the translation units that
+// cannot launch the kernel themselves (the float64 GLM step, rr_glm64.hip)
+int rr_launch_transpose_f64(rr_ctx *c, const double *P, int64_t rows, int64_t ldp, double *Pt, int64_t ldt, int64_t cols_pad,
+                            int64_t rows_pad) {
+    hipLaunchKernelGGL(rr_transpose_f64_kernel, dim3((unsigned)(cols_pad / 64), (unsigned)(rows_pad / 64)), dim3(256), 0, c->stream, P,
+                       rows, ldp, Pt, ldt);
+    RR_CHECK_HIP(hipGetLastError());
+    return RR_OK;
+}
+
 // one wave per row: dot[r] = P[r] . m;  MODE 1 additionally out[r] = U[r] . P[r]
 template <int MODE>
 __global__ void __launch_bounds__(256)
@@ -4149,7 +4159,7 @@ void rr_glm_sgd_destroy(rr_glm_sgd *o) {
 // of _elbo (slm.py:160-197) and predict_moments (slm.py:240-244) in float64 -- the reference's arithmetic end to end for
 // concatenations with a dtype="f64" child (north star: 1e-5 relative in fp64).  The same data flow as rr_featmat /
 // pass2_run64: every child writes its column block, P^T by a transposing pass, U = P C on rr_gemm_tn_f64_kernel, the
-// float64 epilogue kernels above.  Written for the resident fit (CatFitState): no GLM step, no split engines.
+// float64 epilogue kernels above.  Written for the resident fit (CatFitState); the GLM step on it is rr_glm64.hip.  No split engines.
 // =============================================================================================
 // (struct rr_featmat64: rr_internal.h -- the centre bases' float64 entry points of rr_centres.hip share it)
 
@@ -4218,18 +4228,20 @@ int rr_fm64_claim(rr_featmat64 *fm, int64_t col0, int64_t width, const char *who
     fm->covered += width;
     return RR_OK;
 }
-#define RR_FM64_REQUIRE_FILLED(fm, who)                                                                             \
-    RR_REQUIRE((fm)->rows == 0 || (fm)->covered == (fm)->F,                                                         \
-               who ": only %lld of the %d columns were written since rr_featmat64_begin", (long long)(fm)->covered, (fm)->F)
+// (RR_FM64_REQUIRE_FILLED: rr_internal.h -- the GLM step of rr_glm64.hip checks the same)
 
 static void fm64_free_scratch(rr_featmat64 *fm) {
+    rr_glm64_scratch_free(fm->glm);
+    fm->glm = nullptr;
+    fm->have_edphi = false;
+    fm->have_post = false;
     void *q[] = {fm->Pt, fm->U, fm->Cp, fm->Craw, fm->m, fm->dot, fm->err, fm->sq, fm->vf};
     for (void *x : q)
         if (x) (void)hipFree(x);
     fm->Pt = fm->U = fm->Cp = fm->Craw = fm->m = fm->dot = fm->err = fm->sq = fm->vf = nullptr;
 }
 
-static int fm64_scratch(rr_featmat64 *fm) {
+int rr_fm64_scratch(rr_featmat64 *fm) {
     if (fm->Pt) return RR_OK;
     const int64_t Fp = fm->ld;
     hipError_t ea = hipMalloc((void **)&fm->Pt, (size_t)Fp * fm->max_rows * 8);
@@ -4301,6 +4313,7 @@ int rr_featmat64_begin(rr_featmat64 *fm, int64_t rows) {
     fm->spans.clear();
     fm->centres_puts.clear();
     fm->have_rows = false;
+    fm->have_edphi = false;  // (a GLM step's EdPhi belongs to the rows it was formed from)
     // the children overwrite every column of [0, F) for the rows [0, rows) (checked by the consumers); the padding is ours:
     // pad rows up to the next multiple of 128 (SYRK k-blocks, GEMM tiles) and the pad columns [F, ld) of the data rows
     if (fm->rows_pad > rows)
@@ -4440,7 +4453,7 @@ int rr_featmat64_pass2_begin(rr_featmat64 *fm, const double *m, const double *C,
     RR_REQUIRE(fm != nullptr && m != nullptr && C != nullptr, "rr_featmat64_pass2_begin: null argument");
     rr_ctx *c = fm->ctx;
     RR_CHECK_HIP(hipSetDevice(c->device));
-    int rc = fm64_scratch(fm);
+    int rc = rr_fm64_scratch(fm);
     if (rc != RR_OK) return rc;
     const int64_t F = fm->F, Fp = fm->ld;
     RR_CHECK_HIP(hipStreamSynchronize(c->stream));
@@ -4455,14 +4468,17 @@ int rr_featmat64_pass2_begin(rr_featmat64 *fm, const double *m, const double *C,
     RR_CHECK_HIP(hipGetLastError());
     RR_CHECK_HIP(hipMemsetAsync(fm->sq, 0, 8, c->stream));
     fm->have_rows = false;
+    fm->have_edphi = false;  // (m and the products that follow overwrite what a GLM step left in the shared scratch)
+    fm->have_post = true;
     return RR_OK;
 }
 
 int rr_featmat64_pass2_rows(rr_featmat64 *fm, const void *dy, int y_dtype) {
-    RR_REQUIRE(fm != nullptr && fm->Pt != nullptr, "rr_featmat64_pass2_rows: call rr_featmat64_pass2_begin first");
+    RR_REQUIRE(fm != nullptr && fm->Pt != nullptr && fm->have_post, "rr_featmat64_pass2_rows: call rr_featmat64_pass2_begin first");
     RR_FM64_REQUIRE_FILLED(fm, "rr_featmat64_pass2_rows");
     RR_REQUIRE(dy != nullptr && (y_dtype == RR_F32 || y_dtype == RR_F64), "rr_featmat64_pass2_rows: bad y");
     fm->have_rows = true;
+    fm->have_edphi = false;
     if (fm->rows == 0) return RR_OK;
     rr_ctx *c = fm->ctx;
     RR_CHECK_HIP(hipSetDevice(c->device));
@@ -4545,11 +4561,14 @@ int rr_featmat64_pass2_end(rr_featmat64 *fm, double *sqErr) {
 
 // (Ey, Vf) = (P m, rowsum((P C) o P)) for the rows currently in the matrix (after rr_featmat64_pass2_begin), host float64
 int rr_featmat64_predict_rows(rr_featmat64 *fm, double *Ey, double *Vf) {
-    RR_REQUIRE(fm != nullptr && fm->Pt != nullptr && Ey != nullptr && Vf != nullptr, "rr_featmat64_predict_rows: bad argument");
+    RR_REQUIRE(fm != nullptr && fm->Pt != nullptr && fm->have_post && Ey != nullptr && Vf != nullptr,
+               "rr_featmat64_predict_rows: bad argument (rr_featmat64_pass2_begin first)");
     RR_FM64_REQUIRE_FILLED(fm, "rr_featmat64_predict_rows");
     if (fm->rows == 0) return RR_OK;
     rr_ctx *c = fm->ctx;
     RR_CHECK_HIP(hipSetDevice(c->device));
+    fm->have_rows = false;   // U = P C is formed anew below; neither a second pass' rows nor a GLM step's EdPhi survive it
+    fm->have_edphi = false;
     int rc = fm64_products(fm);
     if (rc != RR_OK) return rc;
     hipLaunchKernelGGL(rr_rows64_kernel<1>, dim3((unsigned)((fm->rows + 3) / 4)), dim3(256), 0, c->stream, fm->P, fm->U, fm->m,

@@ -252,8 +252,20 @@ struct rr_featmat64 {
     double *Pt = nullptr, *U = nullptr, *Cp = nullptr, *Craw = nullptr, *m = nullptr, *dot = nullptr, *err = nullptr,
            *sq = nullptr, *vf = nullptr;
     bool have_rows = false;
+    bool have_post = false;  // pass2_begin has put (m, C) into the scratch (a GLM step allocates the same scratch without them)
+    // the GLM step (rr_glm64.hip): its scratch (Glm64Scratch, allocated by the first step, freed with the second pass') and
+    // whether U holds the last step's EdPhi.  U is one buffer: pass2_begin / pass2_rows / predict_rows clear have_edphi, a
+    // step clears have_rows, so neither side ever consumes what the other left there
+    void *glm = nullptr;
+    bool have_edphi = false;
 };
 int rr_fm64_claim(rr_featmat64 *fm, int64_t col0, int64_t width, const char *who);  // rr_elbo.hip
+int rr_fm64_scratch(rr_featmat64 *fm);   // rr_elbo.hip: the second pass' scratch (Pt, U, ...), allocated on first use
+void rr_glm64_scratch_free(void *p);     // rr_glm64.hip
+// Consumers of the float64 matrix call this first: every column of [0, F) must have been put since rr_featmat64_begin.
+#define RR_FM64_REQUIRE_FILLED(fm, who)                                                                             \
+    RR_REQUIRE((fm)->rows == 0 || (fm)->covered == (fm)->F,                                                         \
+               who ": only %lld of the %d columns were written since rr_featmat64_begin", (long long)(fm)->covered, (fm)->F)
 // rr_featmat_put_rff with the length scales in device memory (rr_featmat.hip; the resident SVI loop of rr_elbo.hip)
 int rr_fm_put_rff_dev(rr_featmat *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *dls, int n_ls,
                       int64_t col0, const double *dshift = nullptr, double sgn = 0.0);

@@ -1948,6 +1948,10 @@ struct Gemm64Args {
     int subtract;    // 1: D -= A^T B (blocked Cholesky updates) instead of D = A^T B
     int upper_only;  // 1: only tiles with column tile >= row tile (symmetric trailing update, upper triangle kept);
                      // 2: the same without tile (0, 0) (look-ahead Cholesky: that block is updated ahead, rr_posdef.hip)
+    // row slabs of the K loop (gridDim.y of them; one: every caller but the float64 GLM step's Ed product): slab s sums rows
+    // [s kslab, min(K, (s + 1) kslab)) of A and B into D + s slab_stride -- partial tiles, added in slab order by the caller
+    int kslab;             // % 16 == 0; == K with one slab
+    int64_t slab_stride;   // elements between the slabs' outputs
 };
 
 __global__ void __launch_bounds__(G64_THREADS, 2)
@@ -1982,12 +1986,16 @@ rr_gemm_tn_f64_kernel(const Gemm64Args p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lptr_t)(dst + G64_TC * 8), 16, voff, (unsigned)lr * ldb8, 0, 0);
         }
     };
-    const int nkb = p.K / G64_KB;
-    dma_tile(lds, 0);
+    // this workgroup's row slab (blockIdx.y == 0 and the whole K with one slab)
+    const int64_t k0 = (int64_t)blockIdx.y * p.kslab;
+    const int kleft = p.K - (int)k0;
+    RR_DEV_ASSERT(p.kslab % G64_KB == 0 && kleft > 0);
+    const int nkb = (kleft < p.kslab ? kleft : p.kslab) / G64_KB;
+    dma_tile(lds, k0);
     __syncthreads();
     for (int kb = 0; kb < nkb; ++kb) {
         const int cbuf = kb & 1;
-        if (kb + 1 < nkb) dma_tile(lds + (cbuf ^ 1) * (G64_KB * G64_LDB), (int64_t)(kb + 1) * G64_KB);
+        if (kb + 1 < nkb) dma_tile(lds + (cbuf ^ 1) * (G64_KB * G64_LDB), k0 + (int64_t)(kb + 1) * G64_KB);
         const unsigned abase = lds0 + cbuf * (G64_KB * G64_LDB) + aoff;
         const unsigned bbase = lds0 + cbuf * (G64_KB * G64_LDB) + boff;
         KOps64 o0, o1;
@@ -1997,7 +2005,7 @@ rr_gemm_tn_f64_kernel(const Gemm64Args p) {
     }
     // (subtract: the 16 reads of a block row of D are requested together -- written element by element hipcc serialises
     // 64 load -> wait -> store round trips per lane, ~100 us per tile against 7 us of MFMAs at K = 128)
-    double *Dp = p.D + (ca + wr * 64 + (lane >> 4)) * p.ldd + cb + wc_ * 64 + (lane & 15);  // (i, j, e): + (16 i + 4 e) ldd + 16 j
+    double *Dp = p.D + (int64_t)blockIdx.y * p.slab_stride + (ca + wr * 64 + (lane >> 4)) * p.ldd + cb + wc_ * 64 + (lane & 15);  // (i, j, e): + (16 i + 4 e) ldd + 16 j
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         if (p.subtract) {
@@ -2747,6 +2755,8 @@ int rr_launch_gemm_tn_f64(rr_ctx *c, const double *A, int64_t lda, const double 
     g.A = A; g.B = B; g.D = D; g.lda = lda; g.ldb = ldb; g.ldd = ldd; g.K = (int)K; g.ntb = (int)(N / G64_TC);
     g.subtract = subtract;
     g.upper_only = upper_only;
+    g.kslab = (int)K;
+    g.slab_stride = 0;
     // RR_GEMM64_K128=0: the tile kernel for these shapes too (A/B runs)
     static const bool no_k128 = getenv("RR_GEMM64_K128") != nullptr && atoi(getenv("RR_GEMM64_K128")) == 0;
     if (!no_k128 && K == 128 && M == 128 && N % 32 == 0 && (upper_only == 0 || (upper_only == 1 && N == 128))) {
@@ -2756,6 +2766,25 @@ int rr_launch_gemm_tn_f64(rr_ctx *c, const double *A, int64_t lda, const double 
         return RR_OK;
     }
     hipLaunchKernelGGL(rr_gemm_tn_f64_kernel, dim3((unsigned)((M / G64_TC) * g.ntb)), dim3(G64_THREADS), 0, c->stream, g);
+    RR_CHECK_HIP(hipGetLastError());
+    return RR_OK;
+}
+
+// D + s slab_stride = A[rows of slab s]^T B[rows of slab s], s < nslabs: the tile kernel with its K loop cut into row slabs of
+// kslab rows (the last one shorter, never empty) on a second grid dimension, for products with few output tiles and a long
+// K (the float64 GLM step's Ed = dfs^T Phi, rr_glm64.hip, which adds the slabs' partial tiles in slab order afterwards)
+int rr_launch_gemm_tn_f64_slabs(rr_ctx *c, const double *A, int64_t lda, const double *B, int64_t ldb, double *D, int64_t ldd,
+                                int64_t K, int64_t M, int64_t N, int nslabs, int64_t kslab, int64_t slab_stride) {
+    RR_REQUIRE(nslabs >= 1 && nslabs <= 65535 && kslab >= 16 && kslab % 16 == 0 && K % 16 == 0 && M % G64_TC == 0 && N % G64_TC == 0 &&
+               (int64_t)(nslabs - 1) * kslab < K && (int64_t)nslabs * kslab >= K && slab_stride >= M * ldd,
+               "rr_launch_gemm_tn_f64_slabs: bad slab layout");
+    Gemm64Args g;
+    g.A = A; g.B = B; g.D = D; g.lda = lda; g.ldb = ldb; g.ldd = ldd; g.K = (int)K; g.ntb = (int)(N / G64_TC);
+    g.subtract = 0;
+    g.upper_only = 0;
+    g.kslab = (int)kslab;
+    g.slab_stride = slab_stride;
+    hipLaunchKernelGGL(rr_gemm_tn_f64_kernel, dim3((unsigned)((M / G64_TC) * g.ntb), (unsigned)nslabs), dim3(G64_THREADS), 0, c->stream, g);
     RR_CHECK_HIP(hipGetLastError());
     return RR_OK;
 }

@@ -32,7 +32,7 @@ from sklearn.utils import check_random_state
 from sklearn.utils.validation import check_array, check_is_fitted, check_X_y
 
 from . import _hip
-from .basis_functions import LinearBasis, MinibatchFeatures
+from .basis_functions import LinearBasis, MinibatchFeatures, MinibatchFeatures64
 from .btypes import Bound, Parameter, Positive
 from .likelihoods import Bernoulli, Binomial, Gaussian, Poisson
 from .optimize import logtrick_sgd, sgd, structured_sgd
@@ -152,11 +152,24 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         per component, 2 Xdim coordinates [mean | length scales] -- whenever the shape is in range (rr_glm_svi_supported_gm).
         Under this value a FastFoodGM child of Xdim <= 8, which the chain kernel's mixture mode does not serve, stays resident
         through that dense equivalent (rr_featmat_put_gm), so such a fit has the step-per-call loop as well: out of range,
-        between ranks or with minibatches split over ``devices=``.  Any other value: ValueError at ``fit``."""
+        between ranks or with minibatches split over ``devices=``.  Any other value: ValueError at ``fit``.
+    dtype : "f32" (default) | "f64"
+        Arithmetic of the SVI step and of the latent samples of the prediction calls.  "f32": everything above.  "f64": the
+        step runs on the float64 feature matrix (rr_featmat64_glm_step_draws: features, the three products on the f64 matrix
+        cores, the likelihood terms and every sum in float64, in a fixed order), targets and the binomial's n are staged as
+        float64, the reference's draws stay float64, and ``_sample_matrix`` projects in float64 -- a seeded fit reproduces
+        the reference's to ~1e-9 instead of ~1e-4.  The basis children's own ``dtype`` does not matter: the float64 matrix
+        evaluates random Fourier, centre and polynomial children in float64 (the latter two as device children under
+        ``resident_bases="all"``); FastFood children and inputs of more than 128 columns go through their own ``transform``
+        in their own arithmetic.  ``fit`` takes the host loop around ``_elbo``, one library call per step; the look-ahead
+        stages of the f32 pipeline (draws, uploads and gathers made a step ahead on worker threads) are left out in this mode:
+        batch, draws and step follow each other on the calling thread, in the reference's order.  Refused with ValueError at
+        ``fit``, before any device call: ``sampler="device"``, ``devices=``, ``distributed=True``, ``predict_engine="device"``,
+        a split ``gram_engine`` and ``fused_bases`` other than "fourier".  Any other value of ``dtype``: ValueError at ``fit``."""
 
     def __init__(self, likelihood=Gaussian(), basis=LinearBasis(), K=10, maxiter=3000, batch_size=10, updater=None,
                  nsamples=50, nstarts=500, random_state=None, sampler="host", distributed=False, gram_engine=None,
-                 devices=None, predict_engine="host", resident_bases="fourier", fused_bases="fourier"):
+                 devices=None, predict_engine="host", resident_bases="fourier", fused_bases="fourier", dtype="f32"):
         self.likelihood = likelihood
         self.basis = basis
         self.K = K
@@ -173,12 +186,37 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         self.predict_engine = predict_engine
         self.resident_bases = resident_bases
         self.fused_bases = fused_bases
+        self.dtype = dtype
         self.random_ = check_random_state(self.random_state)
 
     def fit(self, X, y, likelihood_args=()):
         """Learn the posterior mixture and the hyper-parameters (glm.py:141-203)."""
+        self._check_dtype()   # (before the engine scope, which opens the device)
         with self._engine_scope():
             return self._fit(X, y, likelihood_args)
+
+    def _f64(self):
+        return getattr(self, "dtype", "f32") == "f64"
+
+    def _check_dtype(self):
+        """dtype="f64": everything the float64 step does not serve is refused here, before any device call."""
+        dtype = getattr(self, "dtype", "f32")
+        if dtype not in ("f32", "f64"):
+            raise ValueError("dtype must be 'f32' or 'f64'")
+        if dtype == "f32":
+            return
+        if self.sampler != "host":
+            raise ValueError("dtype='f64' needs sampler='host' (the device sampler draws float32)")
+        if getattr(self, "devices", None) is not None:
+            raise ValueError("dtype='f64' does not run over devices=")
+        if self.distributed:
+            raise ValueError("dtype='f64' does not run with distributed=True")
+        if getattr(self, "predict_engine", "host") != "host":
+            raise ValueError("dtype='f64' needs predict_engine='host'")
+        if getattr(self, "gram_engine", None) not in (None, "f32"):
+            raise ValueError("dtype='f64' has no split gram_engine (the float64 matrix has none)")
+        if getattr(self, "fused_bases", "fourier") != "fourier":
+            raise ValueError("dtype='f64' needs fused_bases='fourier' (the fused loop has its own float64 range)")
 
     def _group(self):
         if getattr(self, "devices", None) is None:
@@ -256,6 +294,8 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         # batch -- the order in which a sequential run consumes the stream -- and hands them over with the batch, so
         # the ~12 ms of randn per config-5 step overlap the kernels instead of preceding them.
         prefetch = self._ahead if (self.sampler == "device" or self._prefetch_draws) else False
+        if self._f64():   # no look-ahead stages in float64: batch, draws and step in turn on this thread
+            prefetch = False
         if fused:   # the worker thread cuts the batches and (reference's stream) makes the draws; the loop uploads them in blocks
             prefetch = [self._draw_ahead] if (self.sampler != "device" and self._prefetch_draws) else False
         # (RR_GLM_DRAW_UPLOAD=0: measurement switch, the step uploads its draws itself)
@@ -466,11 +506,13 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
 
     def _reference_draws(self, out=None):
         """The step's standard normals from `random_` in the reference's order (glm.py:300): randn(L, D) per component.
-        out: a (K L, D) float32 array to fill (the minibatch pipeline's ring, `_draw_ahead`)."""
+        out: a (K L, D) float32 array to fill (the minibatch pipeline's ring, `_draw_ahead`).  dtype="f64": float64 (K L, D), the
+        same stream in the same order, unrounded."""
         K, L_, D = self.K, self.nsamples, self.D_
+        ft = np.float64 if self._f64() else np.float32   # dtype="f64": the reference's float64 normals as they are
         if self._native_draws:  # the same K consecutive randn(L, D) as one call of the library's generator (bit-identical)
-            return _hip.legacy_randn(self.random_, K * L_ * D, np.float32, out=out).reshape(K * L_, D)
-        e = np.empty((K * L_, D), dtype=np.float32) if out is None else out
+            return _hip.legacy_randn(self.random_, K * L_ * D, ft, out=out).reshape(K * L_, D)
+        e = np.empty((K * L_, D), dtype=ft) if out is None else out
         for k in range(K):
             e[k * L_:(k + 1) * L_] = self.random_.randn(L_, D)
         return e
@@ -557,6 +599,8 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
             if g is not None:
                 from . import multigpu
                 f = multigpu.ShardedMinibatchFeatures(self.basis, g, batch_size=self.batch_size)
+            elif self._f64():
+                f = MinibatchFeatures64(self.basis, getattr(self, "resident_bases", "fourier"))
             else:
                 f = MinibatchFeatures(self.basis)
             self.__dict__["_mbf"] = f
@@ -809,6 +853,8 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
             if g is not None:
                 from . import multigpu
                 served = multigpu.ShardedMinibatchFeatures(self.basis, g)
+            elif self._f64():
+                served = MinibatchFeatures64(self.basis, getattr(self, "resident_bases", "fourier"))
             else:
                 served = MinibatchFeatures(self.basis)
             srv = self.__dict__["_serve_feats"] = (os.getpid(), served)
