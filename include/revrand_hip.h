@@ -632,6 +632,41 @@ int rr_glm_svi_starts(rr_glm_svi *s, int ncand, const int *d_idx, const double *
 int rr_glm_svi_read(rr_glm_svi *s, double *z, double *objs, double *norms, int64_t *steps);
 void rr_glm_svi_destroy(rr_glm_svi *s);
 
+/* ---- the same loop again for WIDE bases: a fixed chain of kernels per step (rr_svi_wide.hip) ------------------------------
+ * rr_glm_svi holds a component's whole state in one CU's LDS, so minibatch x F <= 8192: at the reference's report shapes (batch
+ * 10, nbases 256 ... 8192, F = 512 ... 16384) only F = 512 is in its range.  rr_glm_sviw keeps rr_glm_svi's contract -- the z
+ * layout, the children table, the updater and likelihood ids, dlconst, bmag, the caller's draws or the device generator as the
+ * same function of (seed, step, sample, feature) -- and runs a step as FOUR kernels on the context's stream, `steps` of them queued
+ * per call; no workgroup waits for another inside a kernel, the kernel boundary is the only ordering.  The basis is cut into
+ * items (rr_glm_sviw_plan); every sum over the basis is stored per (item, component) and added in item order by the next kernel:
+ * no floating-point atomics, a fit is bitwise reproducible and does not depend on how it is cut into rr_glm_sviw_run calls.
+ * Children: RR_SGD_CHILD_RFF (Xdim <= 128) and RR_SGD_CHILD_LINEAR (d <= 128); any other kind: RR_ERR_INVALID naming the child.
+ * rr_glm_sviw_supported (no device needed): K <= 32, nsamples <= 128, minibatch <= 64, F <= 32768, <= 16 children, and the
+ * partial sums of one step (items x K x nsamples x minibatch doubles) within 2 GiB.
+ * rr_glm_sviw_plan (host only): the work items of a step, items[3 i ..] = (child, first frequency or column, count).  kind[c]:
+ * RR_SGD_CHILD_RFF / _LINEAR; n[c]: the child's frequencies (it has 2 n columns) or a linear child's columns (ones column
+ * included); d[c]: its columns of X.  A random Fourier item owns frequencies [j0, j0 + count) and BOTH their columns; a linear
+ * child is one item; no item straddles a child.  The width is the largest count <= 64 whose item fits the kernels' LDS budget
+ * (RR_SVIW_ITEM=<frequencies> replaces the 64: a test and measurement switch).  cap: triples `items` holds (items may be NULL);
+ * info = (items, width, LDS bytes of the largest item, LDS budget). */
+typedef struct rr_glm_sviw rr_glm_sviw;
+int rr_glm_sviw_supported(int F, int K, int L, int M, int n_children, int dsum, int n_ls);
+int rr_glm_sviw_plan(int n_children, const int *kind, const int *n, const int *d, int K, int L, int M, int cap, int *items,
+                     int64_t info[4]);
+int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                       const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K,
+                       int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
+                       const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
+                       rr_glm_sviw **out);
+/* As their rr_glm_svi_ namesakes.  run queues steps x (A, B, C, D) and returns; starts queues (A, B, D) per candidate back to
+ * back and synchronises once. */
+int rr_glm_sviw_set_start(rr_glm_sviw *s, const double *z0, const double *lower, const double *upper, const unsigned char *is_log);
+int rr_glm_sviw_run(rr_glm_sviw *s, int64_t steps, const int *d_idx, const float *dE, uint64_t seed, uint64_t key0);
+int rr_glm_sviw_starts(rr_glm_sviw *s, int ncand, const int *d_idx, const double *cand_host, const float *dE, uint64_t seed,
+                       uint64_t key0, double *objs_host);
+int rr_glm_sviw_read(rr_glm_sviw *s, double *z, double *objs, double *norms, int64_t *steps);
+void rr_glm_sviw_destroy(rr_glm_sviw *s);
+
 /* ---- arithmetic of the f32 Gram (Phi^T Phi of slm.py:145-150 for "f32" bases) -------------------
  * RR_GRAM_F32 (default): f32 features, v_mfma_f32_32x32x2_f32, f32 accumulation per K-split -- bitwise an fmaf chain.
  * RR_GRAM_BF16X3 / RR_GRAM_BF16X4: each f32 feature value is split into bf16 hi + lo and the Gram accumulates

@@ -233,6 +233,22 @@ SIGNATURES = {
     "rr_glm_svi_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.POINTER(ctypes.c_int64)]),
     "rr_glm_svi_destroy": (None, [ctypes.c_void_p]),
+    "rr_glm_sviw_supported": (ctypes.c_int, [ctypes.c_int] * 7),
+    "rr_glm_sviw_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    "rr_glm_sviw_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_int64, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]),
+    "rr_glm_sviw_set_start": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rr_glm_sviw_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                       ctypes.c_uint64]),
+    "rr_glm_sviw_starts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]),
+    "rr_glm_sviw_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.POINTER(ctypes.c_int64)]),
+    "rr_glm_sviw_destroy": (None, [ctypes.c_void_p]),
     "rr_posterior_available": (ctypes.c_int, []),
     "rr_set_gram_engine": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "rr_get_gram_engine": (ctypes.c_int, [ctypes.c_void_p]),
@@ -1418,9 +1434,7 @@ class FusedSvi(object):
         par[:len(updater_par)] = updater_par
         self.maxiter = int(maxiter)
         h = ctypes.c_void_p()
-        create = self.lib.rr_glm_svi_create_all if all_children else self.lib.rr_glm_svi_create
-        if gm_children:
-            create = self.lib.rr_glm_svi_create_gm
+        create = self._creator(all_children, gm_children)
         _check(self.lib, create(
             dev.ctx, nk, ctypes.cast(kids, ctypes.c_void_p), ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(dts, ctypes.c_void_p),
             ctypes.cast(lds, ctypes.c_void_p), int(N), _ptr(dy), _ptr(drowarg), _ptr(dlconst), rr_dtype(dy.dtype), self.K, self.L, self.M,
@@ -1429,22 +1443,35 @@ class FusedSvi(object):
             par.ctypes.data_as(ctypes.c_void_p), self.maxiter, float(bmag), ctypes.byref(h)))
         self.h = h
 
+    _prefix = "rr_glm_svi_"   # (WideSvi: the same five calls of rr_glm_sviw_)
+
+    def _creator(self, all_children, gm_children):
+        if gm_children:
+            return self.lib.rr_glm_svi_create_gm
+        return self.lib.rr_glm_svi_create_all if all_children else self.lib.rr_glm_svi_create
+
     def set_start(self, z0, lower, upper, is_log):
         arrs = [np.ascontiguousarray(z0, dtype=np.float64), np.ascontiguousarray(lower, dtype=np.float64),
                 np.ascontiguousarray(upper, dtype=np.float64), np.ascontiguousarray(is_log, dtype=np.uint8)]
         if any(a.shape != (self.np_,) for a in arrs):
             raise ValueError("set_start: %d coordinates expected" % self.np_)
-        _check(self.lib, self.lib.rr_glm_svi_set_start(self.h, *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs]))
+        _check(self.lib, getattr(self.lib, self._prefix + "set_start")(self.h, *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs]))
 
     def run(self, steps, didx, dE=None, seed=0, key0=0):
         """`steps` SGD steps in one launch (asynchronous): didx a device int32 (steps, M) buffer, dE device float32 draws or None."""
-        _check(self.lib, self.lib.rr_glm_svi_run(self.h, int(steps), _ptr(didx), None if dE is None else _ptr(dE), int(seed), int(key0)))
+        self._run(steps, didx, dE, seed, key0)
+
+    def _run(self, steps, didx, dE, seed, key0):
+        _check(self.lib, getattr(self.lib, self._prefix + "run")(self.h, int(steps), _ptr(didx), None if dE is None else _ptr(dE), int(seed), int(key0)))
 
     def starts(self, didx, cand, dE=None, seed=0, key0=0):
         """-ELBO of every candidate row of `cand` (ncand, np; x space) on its own minibatch / draws: one launch."""
+        return self._starts(didx, cand, dE, seed, key0)
+
+    def _starts(self, didx, cand, dE, seed, key0):
         cand = np.ascontiguousarray(cand, dtype=np.float64)
         out = np.empty(cand.shape[0])
-        _check(self.lib, self.lib.rr_glm_svi_starts(self.h, cand.shape[0], _ptr(didx), cand.ctypes.data_as(ctypes.c_void_p),
+        _check(self.lib, getattr(self.lib, self._prefix + "starts")(self.h, cand.shape[0], _ptr(didx), cand.ctypes.data_as(ctypes.c_void_p),
                                                     None if dE is None else _ptr(dE), int(seed), int(key0),
                                                     out.ctypes.data_as(ctypes.c_void_p)))
         return out
@@ -1452,20 +1479,71 @@ class FusedSvi(object):
     def read(self):
         z, objs, norms = np.empty(self.np_), np.empty(self.maxiter), np.empty(self.maxiter)
         n = ctypes.c_int64()
-        _check(self.lib, self.lib.rr_glm_svi_read(self.h, z.ctypes.data_as(ctypes.c_void_p), objs.ctypes.data_as(ctypes.c_void_p),
+        _check(self.lib, getattr(self.lib, self._prefix + "read")(self.h, z.ctypes.data_as(ctypes.c_void_p), objs.ctypes.data_as(ctypes.c_void_p),
                                                   norms.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n)))
         return z, objs[:n.value], norms[:n.value]
 
     def close(self):
         h, self.h = getattr(self, "h", None), None
         if h:
-            self.lib.rr_glm_svi_destroy(h)
+            getattr(self.lib, self._prefix + "destroy")(h)
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+class WideSvi(FusedSvi):
+    """The same loop for wide bases: a fixed chain of four kernels per step, many steps queued per call (rr_glm_sviw,
+    rr_svi_wide.hip).  FusedSvi's arguments and its five methods; children: "rff" and "linear" tuples only (anything else is
+    refused by rr_glm_sviw_create with a message naming the child)."""
+
+    _prefix = "rr_glm_sviw_"
+
+    def _creator(self, all_children, gm_children):
+        if all_children or gm_children:
+            raise ValueError("the wide loop takes random Fourier and linear children only")
+        return self.lib.rr_glm_sviw_create
+
+    def run(self, steps, didx, dE=None, seed=0, key0=0):
+        """`steps` x (the chain of four kernels) queued on the context's stream (asynchronous)."""
+        self._run(steps, didx, dE, seed, key0)
+
+    def starts(self, didx, cand, dE=None, seed=0, key0=0):
+        """-ELBO of every candidate: the chain's objective-only prefix per candidate, one synchronisation at the end."""
+        return self._starts(didx, cand, dE, seed, key0)
+
+
+def sviw_supported(F, K, L, M, n_children, dsum, n_ls):
+    """rr_glm_sviw_supported: the range of WideSvi (needs no device)."""
+    return bool(load_library().rr_glm_sviw_supported(int(F), int(K), int(L), int(M), int(n_children), int(dsum), int(n_ls)))
+
+
+def sviw_plan(children, K, L, M):
+    """rr_glm_sviw_plan (host only): the work items of one step of the wide loop.  children: ("rff", n frequencies, Xdim) |
+    ("linear", columns of X, onescol) in concatenation order.  Returns (items, info): items a list of (child, first frequency or
+    column, count), info a dict with the item width in frequencies, the LDS bytes of the largest item and the budget."""
+    lib = load_library()
+    nk = len(children)
+    kind, n, d = (ctypes.c_int * nk)(), (ctypes.c_int * nk)(), (ctypes.c_int * nk)()
+    for i, ch in enumerate(children):
+        if ch[0] == "rff":
+            kind[i], n[i], d[i] = 0, int(ch[1]), int(ch[2])
+        elif ch[0] == "linear":
+            kind[i], n[i], d[i] = 1, int(ch[1]) + (1 if ch[2] else 0), int(ch[1])
+        else:
+            raise ValueError("sviw_plan: child %d: %r is not taken by the wide loop" % (i, ch[0]))
+    info = (ctypes.c_int64 * 4)()
+    _check(lib, lib.rr_glm_sviw_plan(nk, ctypes.cast(kind, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p),
+                                     ctypes.cast(d, ctypes.c_void_p), int(K), int(L), int(M), 0, None, info))
+    cap = int(info[0])
+    items = (ctypes.c_int * (3 * cap))()
+    _check(lib, lib.rr_glm_sviw_plan(nk, ctypes.cast(kind, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p),
+                                     ctypes.cast(d, ctypes.c_void_p), int(K), int(L), int(M), cap, ctypes.cast(items, ctypes.c_void_p), info))
+    out = [(items[3 * i], items[3 * i + 1], items[3 * i + 2]) for i in range(cap)]
+    return out, {"items": cap, "width": int(info[1]), "lds_bytes": int(info[2]), "lds_budget": int(info[3])}
 
 
 def svi_supported(F, K, L, M, n_children, dsum, n_ls):

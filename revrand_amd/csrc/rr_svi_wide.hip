@@ -1,0 +1,1012 @@
+// The small-minibatch regime of GeneralizedLinearModel.fit (rr_svi.hip) for WIDE bases: the reference's report runs batch 10,
+// K = 10, 50 samples at nbases 256 ... 8192, F = 512 ... 16384, where (m, C) of one component alone no longer fits a CU's LDS.
+//
+// rr_svi.hip keeps K workgroups inside one kernel and orders them with device-scope barriers; that needs co-residency and
+// does not grow.  Here NO workgroup ever waits for another: a step is a fixed chain of FOUR kernels on the context's stream
+// and the kernel boundary is the only ordering between workgroups; `steps` chains are queued per library call.  The basis is
+// cut into ITEMS (rr_glm_sviw_plan: a run of frequencies of one random Fourier child with BOTH their columns, or one whole
+// linear child), and every sum over the basis is "each (item, component) workgroup stores its partial, a later kernel adds
+// the partials in item order": no floating-point atomics, the same bits every run and for every cut of a fit into calls.
+//
+//   A  grid (items, K)   mk, sk of the item's columns; the minibatch rows gathered by index; Phi of the item (component 0's
+//                        workgroup stores it for C); the draws of component k (the caller's or svi_draw's); the item's partial
+//                        of fs[k, l, r] = ws Phi^T; its partial of row k of the mixture's cross terms q and of sum (m^2 + C)
+//   B  grid (blocks, K)  fs = the partials in item order; dfs and the log-likelihood sums per block (svi_lik's formulas);
+//                        block 0 of component k: q[k][.] and sum (m^2 + C) per child in item order
+//   C  grid (items, K)   log N, log z, alpha from q; D_r = sum_l dfs, Q = dfs^T e of the item; Edm, EdC; the gradient of the
+//                        item's 2 w coordinates of component k, log trick, |g|^2 partial, bounds, updater, clip; the item's
+//                        partial of the child's length-scale contractions
+//   D  one workgroup     the partials of C in item order; the shared coordinates (regularisers, Gaussian variance, length
+//                        scales); the step's -ELBO and |g|
+//
+// x = from_log(z) lives in HBM twice, by step parity: a step reads x[t & 1] and writes x[(t + 1) & 1] (C its own coordinates,
+// D the shared ones), so no kernel reads what a neighbour of the same launch writes.  rr_glm_sviw_starts runs A, B and D
+// (objective only) per candidate, the candidate's x in place of x[t & 1].
+// Everything is float64 (the draws are float32 values); no lgamma, no pow: dlconst and Adam's bias come from the host.
+#include "rr_internal.h"
+
+#include <algorithm>
+#include <cstdlib>
+
+#define SW_MAXCHILD 16
+#define SW_MAXK 32
+#define SW_MAXL 128
+#define SW_MAXM 64
+#define SW_MAXF 32768
+#define SW_MAXD 128
+#define SW_THREADS 512
+#define SW_WAVES (SW_THREADS / 64)
+#define SW_ITEM_DEFAULT 64                   // frequencies per item at most (LDS permitting)
+#define SW_LDS_BUDGET (156 * 1024)           // what an item may take of a CU's 160 KiB
+#define SW_SCRATCH_MAX ((int64_t)2 << 30)    // the partials of fs (items K L M doubles) stay below this
+#define SW_LAUNCHES_PER_STEP 4
+#define SW_LAUNCHES_PER_START 3
+
+namespace {
+
+struct SwChild {
+    int kind, col0, width, d, n, n_ls, ls0, onescol, x_f64, item0, nitems;
+    const void *X;
+    int64_t ldx;
+    const double *W;   // RFF: raw (d, n) row-major on the device
+};
+
+struct SwItem {
+    int child, j0, cnt;   // RFF: frequencies [j0, j0 + cnt) and both their columns; linear: columns [j0, j0 + cnt) = all of them
+};
+
+struct SwArgs {
+    const SwChild *kid;
+    const SwItem *items;
+    int nitems, nkids, F, K, L, M, lik, n_lik, n_ls, ns, updater, y_f64, maxls, nbx, objective_only;
+    int64_t np, N;
+    const void *y, *rowarg;
+    const double *lconst;
+    double *z, *s1, *s2;
+    const double *lower, *upper;
+    const unsigned char *islog;
+    const double *xin;   // x of this step (or the candidate)
+    double *xout;        // x of the next step
+    double *Phi, *fsp, *qp, *Rp, *dfs, *llp, *qf, *Rk, *n2p, *glsp;
+    const float *E;      // this step's draws (K L, F) or null
+    const int *idx;      // this step's rows (M)
+    double *obj, *norm;  // where this step's (candidate's) record goes
+    double up[4], bmag, b1t, b2t;
+    uint64_t stepkey;
+};
+
+// ---- the same device functions as rr_svi.hip (its kernel's own copies stay where they are: sharing them through a header
+// would change that kernel's code generation) ---------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t sw_splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// the draw of rr_glm_draw_kernel (rr_elbo.hip) for (seed, step, counter): svi_draw
+__device__ __forceinline__ float sw_draw(uint64_t stepkey, uint64_t ctr) {
+    const uint64_t h = sw_splitmix64(stepkey ^ ctr);
+    const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);
+    const float u2 = (float)(uint32_t)((h >> 8) & 0xFFFFFFu) * (1.0f / 16777216.0f);
+    return sqrtf(-2.0f * __logf(u1)) * __builtin_amdgcn_cosf(u2);
+}
+
+__device__ __forceinline__ double sw_softplus(double f) { return fmax(f, 0.0) + log1p(exp(-fabs(f))); }
+__device__ __forceinline__ double sw_expit(double f) {
+    const double e = exp(-fabs(f));
+    return f >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+}
+
+// svi_lik: d loglike / d f and the f-dependent part of loglike (Gaussian: the squared error)
+__device__ __forceinline__ void sw_lik(int lik, double f, double y, double n, double ivar, double &df, double &ll) {
+    if (lik == RR_LIK_BERNOULLI) {
+        df = y - sw_expit(f);
+        ll = y * f - sw_softplus(f);
+    } else if (lik == RR_LIK_BINOMIAL) {
+        df = y - n * sw_expit(f);
+        ll = y * f - n * sw_softplus(f);
+    } else if (lik == RR_LIK_GAUSSIAN) {
+        const double er = y - f;
+        df = er * ivar;
+        ll = er * er;
+    } else if (lik == RR_LIK_POISSON_EXP) {
+        const double g = exp(f);
+        df = y - g;
+        ll = y * f - g;
+    } else {
+        const double g = fmax(sw_softplus(f), 1e-100);
+        df = sw_expit(f) * (y / g - 1.0);
+        ll = y * log(g) - g;
+    }
+}
+
+typedef __attribute__((address_space(3))) double ldsd;
+typedef __attribute__((address_space(3))) float ldsf;
+
+__device__ __forceinline__ double sw_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// sum over the block in a fixed order; every thread gets it (red: SW_WAVES doubles of LDS)
+__device__ __forceinline__ double sw_block_sum(double v, ldsd *red) {
+    const int tid = threadIdx.x;
+    v = sw_wave_sum(v);
+    __syncthreads();
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    double r = 0.0;
+#pragma unroll
+    for (int w = 0; w < SW_WAVES; ++w) r += red[w];
+    return r;
+}
+
+__device__ __forceinline__ double sw_xval(const SwChild &c, int64_t row, int i) {
+    return c.x_f64 ? ((const double *)c.X)[row * c.ldx + i] : (double)((const float *)c.X)[row * c.ldx + i];
+}
+
+// svi_update: one coordinate's truncation + updater + clip (sgd.py:404-420, :14-330); g is the gradient in z space
+__device__ __forceinline__ double sw_update(const SwArgs &a, double zz, double g, double lo, double hi, double &s1, double &s2) {
+#pragma clang fp contract(off)
+    if (zz <= lo) g = (g <= 0.0 || g != g) ? g : 0.0;
+    if (zz >= hi) g = (g >= 0.0 || g != g) ? g : 0.0;
+    double zn;
+    switch (a.updater) {
+        case RR_UPD_SGD: zn = zz - a.up[0] * g; break;
+        case RR_UPD_ADADELTA: {
+            const double eg2 = a.up[0] * s1 + (1 - a.up[0]) * (g * g);
+            const double dx = -g * sqrt(s2 + a.up[1]) / sqrt(eg2 + a.up[1]);
+            s1 = eg2;
+            s2 = a.up[0] * s2 + (1 - a.up[0]) * (dx * dx);
+            zn = zz + dx;
+        } break;
+        case RR_UPD_ADAGRAD: {
+            const double h = s1 + g * g;
+            s1 = h;
+            zn = zz - a.up[0] * g / (a.up[1] + sqrt(h));
+        } break;
+        case RR_UPD_MOMENTUM: {
+            const double dx = a.up[0] * s1 - a.up[1] * g;
+            s1 = dx;
+            zn = zz + dx;
+        } break;
+        default: {
+            const double m = a.up[1] * s1 + (1 - a.up[1]) * g;
+            const double v = a.up[2] * s2 + (1 - a.up[2]) * (g * g);
+            s1 = m;
+            s2 = v;
+            zn = zz - a.up[0] * (m / a.b1t) / (sqrt(v / a.b2t) + a.up[3]);
+        }
+    }
+    return zn < lo ? lo : (zn > hi ? hi : zn);
+}
+
+// ---- what one item holds in LDS (doubles) in kernel A (stage 0) and kernel C (stage 1) -----------------------------------------
+// A: the gathered rows, W / (2 pi l), Phi, mk, sk, the draws.  C: the same front part (W raw) plus dfs, Q, T, D_r, q, log z,
+// alpha; a linear item of C keeps neither draws nor Q (each draw is used once there: read or made on the fly).
+struct SwLay {
+    size_t Xb, Wl, Phi, mk, sk, Ef, dfs, Q, T, Dr, q, logz, alpha, red, total;
+    int w, wp;
+};
+
+static __host__ __device__ SwLay sw_layout(int rff, int cnt, int d, int K, int L, int M, int stage) {
+    SwLay s;
+    s.w = rff ? 2 * cnt : cnt;
+    s.wp = s.w | 1;   // odd row length of Phi: rows r, r + 1 of one column sit in different banks
+    size_t o = 0;
+    s.Xb = o; o += rff ? (size_t)M * d : 0;
+    s.Wl = o; o += rff ? (size_t)d * cnt : 0;
+    s.Phi = o; o += (size_t)M * s.wp;
+    s.mk = o; o += s.w;
+    s.sk = o; o += s.w;
+    s.Ef = o; o += (rff || stage == 0) ? ((size_t)L * s.w + 1) / 2 : 0;
+    s.dfs = o; o += stage ? (size_t)L * M : 0;
+    s.Q = o; o += (stage && rff) ? (size_t)M * s.w : 0;
+    s.T = o; o += (stage && rff) ? (size_t)M * cnt : 0;
+    s.Dr = o; o += stage ? M : 0;
+    s.q = o; o += stage ? (size_t)K * K : 0;
+    s.logz = o; o += stage ? K : 0;
+    s.alpha = o; o += stage ? K : 0;
+    s.red = o; o += 8;
+    s.total = o;
+    return s;
+}
+
+static size_t sw_item_bytes(int rff, int cnt, int d, int K, int L, int M) {
+    return 8 * std::max(sw_layout(rff, cnt, d, K, L, M, 0).total, sw_layout(rff, cnt, d, K, L, M, 1).total);
+}
+
+// the item's local column cc (< w) in the concatenation
+__device__ __forceinline__ int sw_col(const SwChild &c, const SwItem &it, int cc) {
+    if (c.kind == RR_SGD_CHILD_RFF) return c.col0 + (cc < it.cnt ? it.j0 + cc : c.n + it.j0 + (cc - it.cnt));
+    return c.col0 + it.j0 + cc;
+}
+
+__device__ __forceinline__ void sw_check_item(const SwArgs &a, const SwChild &c, const SwItem &it) {
+    RR_DEV_ASSERT(it.child >= 0 && it.child < a.nkids && it.cnt >= 1 && it.j0 >= 0);
+    RR_DEV_ASSERT(c.col0 >= 0 && c.col0 + c.width <= a.F);
+    RR_DEV_ASSERT(c.kind == RR_SGD_CHILD_RFF ? (it.j0 + it.cnt <= c.n && c.width == 2 * c.n) : (it.j0 == 0 && it.cnt == c.width));
+    RR_DEV_ASSERT(c.ls0 >= 0 && c.ls0 + c.n_ls <= a.n_ls && c.n_ls <= a.maxls);
+}
+
+// the item's draws of component k into LDS (L, w): the caller's or the device generator's -- the counter of rr_glm_draw_kernel
+__device__ __forceinline__ void sw_draws(const SwArgs &a, const SwChild &c, const SwItem &it, int k, int w, ldsf *Ef) {
+    const int tid = threadIdx.x, L = a.L, F = a.F;
+    for (int o = tid; o < L * w; o += SW_THREADS) {
+        const int l = o / w, col = sw_col(c, it, o % w);
+        RR_DEV_ASSERT(col >= c.col0 && col < c.col0 + c.width);
+        const uint64_t ctr = ((uint64_t)k * (uint64_t)L + (uint64_t)l) * (uint64_t)F + (uint64_t)col;
+        Ef[o] = a.E ? a.E[ctr] : sw_draw(a.stepkey, ctr);
+    }
+}
+
+// the minibatch's rows of a random Fourier child's columns of X into LDS (M, d)
+__device__ __forceinline__ void sw_gather(const SwArgs &a, const SwChild &c, ldsd *Xb) {
+    for (int e = threadIdx.x; e < a.M * c.d; e += SW_THREADS) {
+        const int r = e / c.d, i = e % c.d;
+        const int64_t row = a.idx[r];
+        RR_DEV_ASSERT(row >= 0 && row < a.N);
+        Xb[e] = sw_xval(c, row, i);
+    }
+}
+
+// ---- A ------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_a_kernel(const SwArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ double sm[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, ii = blockIdx.x, k = blockIdx.y;
+    const int K = a.K, F = a.F, L = a.L, M = a.M;
+    RR_DEV_ASSERT(ii < a.nitems && k < K);
+    const SwItem it = a.items[ii];
+    const SwChild &c = a.kid[it.child];
+    sw_check_item(a, c, it);
+    const bool rff = c.kind == RR_SGD_CHILD_RFF;
+    const SwLay s = sw_layout(rff, it.cnt, c.d, K, L, M, 0);
+    const int w = s.w, wp = s.wp, cnt = it.cnt;
+    ldsd *b = (ldsd *)sm;
+    ldsd *Xb = b + s.Xb, *Wl = b + s.Wl, *Phi = b + s.Phi, *mk = b + s.mk, *sk = b + s.sk;
+    ldsf *Ef = (ldsf *)(b + s.Ef);
+    const int64_t fk = (int64_t)F * K;
+    const double *xm = a.xin, *xC = a.xin + fk, *xs = a.xin + 2 * fk;
+    for (int cc = tid; cc < w; cc += SW_THREADS) {
+        const int col = sw_col(c, it, cc);
+        mk[cc] = xm[(int64_t)col * K + k];
+        sk[cc] = sqrt(xC[(int64_t)col * K + k]);
+    }
+    if (rff) {
+        sw_gather(a, c, Xb);
+        // W[i][j] / (2 pi l_i): phases in revolutions; the isotropic child has one length scale for every dimension
+        for (int e = tid; e < c.d * cnt; e += SW_THREADS) {
+            const int i = e / cnt, j = e % cnt;
+            const double l = xs[a.nkids + a.n_lik + c.ls0 + (c.n_ls == 1 ? 0 : i)];
+            Wl[e] = c.W[(size_t)i * c.n + it.j0 + j] * (0.15915494309189533576888 / l);
+        }
+    }
+    sw_draws(a, c, it, k, w, Ef);
+    __syncthreads();
+    if (rff) {
+        const double scale = 1.0 / sqrt((double)c.n);
+        for (int e = tid; e < M * cnt; e += SW_THREADS) {
+            const int r = e / cnt, j = e % cnt;
+            double t = 0.0;
+            for (int i = 0; i < c.d; ++i) t = fma(Xb[r * c.d + i], Wl[i * cnt + j], t);
+            double sn, cs;
+            rr_sincos_rev_f64(t, sn, cs);
+            Phi[r * wp + j] = cs * scale;
+            Phi[r * wp + cnt + j] = sn * scale;
+        }
+    } else {
+        RR_DEV_ASSERT(c.width == c.d + c.onescol);
+        for (int e = tid; e < M * w; e += SW_THREADS) {
+            const int r = e / w, j = e % w;
+            const int64_t row = a.idx[r];
+            RR_DEV_ASSERT(row >= 0 && row < a.N);
+            Phi[r * wp + j] = (c.onescol && j == 0) ? 1.0 : sw_xval(c, row, j - c.onescol);
+        }
+    }
+    __syncthreads();
+    if (k == 0)   // Phi does not depend on the component: kernel C reads it back instead of forming it again
+        for (int e = tid; e < M * w; e += SW_THREADS) a.Phi[(size_t)(e / w) * F + sw_col(c, it, e % w)] = Phi[(e / w) * wp + e % w];
+    // the item's partial of fs[k, l, r] = sum_col (m + sqrt(C) e)[l][col] Phi[r][col]
+    double *fsp = a.fsp + ((size_t)ii * K + k) * L * M;
+    for (int o = tid; o < L * M; o += SW_THREADS) {
+        const int l = o / M, r = o % M;
+        double acc = 0.0;
+        for (int cc = 0; cc < w; ++cc) acc = fma(fma(sk[cc], (double)Ef[l * w + cc], mk[cc]), Phi[r * wp + cc], acc);
+        fsp[o] = acc;
+    }
+    // the item's partial of q[k][l] = sum_f log(C_fk + C_fl) + (m_fk - m_fl)^2 / (C_fk + C_fl): one wave per l   glm.py:697-712
+    for (int l = wave; l < K; l += SW_WAVES) {
+        double acc = 0.0;
+        for (int cc = lane; cc < w; cc += 64) {
+            const int64_t col = sw_col(c, it, cc);
+            const double dc = xC[col * K + k] + xC[col * K + l];
+            const double dm = xm[col * K + k] - xm[col * K + l];
+            acc += log(dc) + dm * dm / dc;
+        }
+        acc = sw_wave_sum(acc);
+        if (lane == 0) a.qp[((size_t)ii * K + k) * K + l] = acc;
+    }
+    if (wave == 0) {   // and of sum (m^2 + C) over the child's rows of component k
+        double acc = 0.0;
+        for (int cc = lane; cc < w; cc += 64) acc += mk[cc] * mk[cc] + sk[cc] * sk[cc];
+        acc = sw_wave_sum(acc);
+        if (lane == 0) a.Rp[(size_t)ii * K + k] = acc;
+    }
+}
+
+// ---- B ------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_b_kernel(const SwArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double redm[8];
+    ldsd *red = (ldsd *)redm;
+    const int tid = threadIdx.x, bx = blockIdx.x, k = blockIdx.y, K = a.K, L = a.L, M = a.M, LM = L * M;
+    RR_DEV_ASSERT(bx < a.nbx && k < K);
+    const int64_t fk = (int64_t)a.F * K;
+    const double ivar = a.n_lik ? 1.0 / a.xin[2 * fk + a.nkids] : 0.0;
+    const int o = bx * SW_THREADS + tid;
+    double ll = 0.0;
+    if (o < LM) {
+        const int r = o % M;
+        double fs = 0.0;
+        for (int ii = 0; ii < a.nitems; ++ii) fs += a.fsp[((size_t)ii * K + k) * LM + o];
+        const int64_t row = a.idx[r];
+        RR_DEV_ASSERT(row >= 0 && row < a.N);
+        const double y = a.y_f64 ? ((const double *)a.y)[row] : (double)((const float *)a.y)[row];
+        double n = 0.0;
+        if (a.rowarg) n = a.y_f64 ? ((const double *)a.rowarg)[row] : (double)((const float *)a.rowarg)[row];
+        double df;
+        sw_lik(a.lik, fs, y, n, ivar, df, ll);
+        a.dfs[(size_t)k * LM + o] = df;
+    }
+    ll = sw_block_sum(ll, red);
+    if (tid == 0) a.llp[(size_t)k * a.nbx + bx] = ll;
+    if (bx == 0) {
+        if (tid < K) {
+            double q = 0.0;
+            for (int ii = 0; ii < a.nitems; ++ii) q += a.qp[((size_t)ii * K + k) * K + tid];
+            a.qf[k * K + tid] = q;
+        } else if (tid < K + a.nkids) {
+            const SwChild &c = a.kid[tid - K];
+            RR_DEV_ASSERT(c.item0 >= 0 && c.item0 + c.nitems <= a.nitems);
+            double R = 0.0;
+            for (int ii = c.item0; ii < c.item0 + c.nitems; ++ii) R += a.Rp[(size_t)ii * K + k];
+            a.Rk[(tid - K) * K + k] = R;
+        }
+    }
+}
+
+// log z_l = logsumexp_j log N_jl, log N_jl = -(F log 2 pi + q_jl) / 2, from the full q in LDS   glm.py:221-222
+__device__ __forceinline__ void sw_logz(const SwArgs &a, const ldsd *q, ldsd *logz) {
+    const int tid = threadIdx.x, K = a.K;
+    if (tid < K) {
+        double mx = -INFINITY;
+        for (int j = 0; j < K; ++j) mx = fmax(mx, -0.5 * ((double)a.F * 1.8378770664093453 + q[j * K + tid]));
+        double sm = 0.0;
+        for (int j = 0; j < K; ++j) sm += exp(-0.5 * ((double)a.F * 1.8378770664093453 + q[j * K + tid]) - mx);
+        logz[tid] = log(sm) + mx;
+    }
+    __syncthreads();
+}
+
+// ---- C ------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ double sm[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, ii = blockIdx.x, k = blockIdx.y;
+    const int K = a.K, F = a.F, L = a.L, M = a.M;
+    RR_DEV_ASSERT(ii < a.nitems && k < K);
+    const SwItem it = a.items[ii];
+    const SwChild &c = a.kid[it.child];
+    sw_check_item(a, c, it);
+    const bool rff = c.kind == RR_SGD_CHILD_RFF;
+    const SwLay s = sw_layout(rff, it.cnt, c.d, K, L, M, 1);
+    const int w = s.w, wp = s.wp, cnt = it.cnt;
+    ldsd *b = (ldsd *)sm;
+    ldsd *Xb = b + s.Xb, *Wl = b + s.Wl, *Phi = b + s.Phi, *mk = b + s.mk, *sk = b + s.sk, *dfs = b + s.dfs, *Q = b + s.Q, *T = b + s.T,
+         *Dr = b + s.Dr, *q = b + s.q, *logz = b + s.logz, *alpha = b + s.alpha, *red = b + s.red;
+    ldsf *Ef = (ldsf *)(b + s.Ef);
+    const int64_t fk = (int64_t)F * K;
+    const double *xm = a.xin, *xC = a.xin + fk, *xs = a.xin + 2 * fk;
+    for (int o = tid; o < L * M; o += SW_THREADS) dfs[o] = a.dfs[(size_t)k * L * M + o];
+    for (int cc = tid; cc < w; cc += SW_THREADS) {
+        const int col = sw_col(c, it, cc);
+        mk[cc] = xm[(int64_t)col * K + k];
+        sk[cc] = sqrt(xC[(int64_t)col * K + k]);
+    }
+    for (int e = tid; e < M * w; e += SW_THREADS) Phi[(e / w) * wp + e % w] = a.Phi[(size_t)(e / w) * F + sw_col(c, it, e % w)];
+    for (int o = tid; o < K * K; o += SW_THREADS) q[o] = a.qf[o];
+    if (rff) {
+        sw_gather(a, c, Xb);
+        for (int e = tid; e < c.d * cnt; e += SW_THREADS) Wl[e] = c.W[(size_t)(e / cnt) * c.n + it.j0 + e % cnt];
+        sw_draws(a, c, it, k, w, Ef);
+    }
+    __syncthreads();
+    sw_logz(a, q, logz);
+    if (tid < K) {
+        const double lN = -0.5 * ((double)F * 1.8378770664093453 + q[tid * K + k]);
+        alpha[tid] = exp(lN - logz[k]) + exp(lN - logz[tid]);
+    }
+    // D_r = sum_l dfs[l][r]; Q[r][j] = sum_l dfs[l][r] e[l][j]: the only sums over the samples the gradients need
+    if (tid < M) {
+        double acc = 0.0;
+        for (int l = 0; l < L; ++l) acc += dfs[l * M + tid];
+        Dr[tid] = acc;
+    }
+    if (rff) {
+        for (int o = tid; o < M * w; o += SW_THREADS) {
+            const int r = o / w, cc = o % w;
+            double acc = 0.0;
+            for (int l = 0; l < L; ++l) acc = fma(dfs[l * M + r], (double)Ef[l * w + cc], acc);
+            Q[o] = acc;
+        }
+    }
+    __syncthreads();
+    //   Edm[j] = sum_r D_r Phi[r][j] / L;  EdC[j] = sum_r Q[r][j] Phi[r][j] / (L sk[j])           glm.py:308-310
+    // then the gradient of (m, C)[col][k], the log trick's chain rule, bounds, updater, clip          glm.py:252-256, sgd.py:404-420
+    const double reg = xs[it.child];
+    double n2 = 0.0;
+    for (int p = tid; p < 2 * w; p += SW_THREADS) {
+        const int cov = p >= w, cc = cov ? p - w : p;
+        const int64_t col = sw_col(c, it, cc);
+        double ed = 0.0;
+        if (!cov) {
+            for (int r = 0; r < M; ++r) ed = fma(Dr[r], Phi[r * wp + cc], ed);
+            ed = ed / L;
+        } else if (rff) {
+            for (int r = 0; r < M; ++r) ed = fma(Q[r * w + cc], Phi[r * wp + cc], ed);
+            ed = ed / (L * sk[cc]);
+        } else {
+            // a linear child keeps neither Q nor its draws: sum_r Q[r][j] Phi[r][j] = sum_l e[l][j] (sum_r dfs[l][r] Phi[r][j]), each
+            // draw read (or made) once, by the one thread that owns column j
+            for (int l = 0; l < L; ++l) {
+                double t = 0.0;
+                for (int r = 0; r < M; ++r) t = fma(dfs[l * M + r], Phi[r * wp + cc], t);
+                const uint64_t ctr = ((uint64_t)k * (uint64_t)L + (uint64_t)l) * (uint64_t)F + (uint64_t)col;
+                ed = fma((double)(a.E ? a.E[ctr] : sw_draw(a.stepkey, ctr)), t, ed);
+            }
+            ed = ed / (L * sk[cc]);
+        }
+        const double mkv = xm[col * K + k], Ck = xC[col * K + k];
+        double mix = 0.0;
+        for (int l = 0; l < K; ++l) {
+            const double ic = 1.0 / (Ck + xC[col * K + l]);
+            const double dm = mkv - xm[col * K + l];
+            const double e = dm * ic;
+            mix += (cov ? ic - e * e : ic * dm) * alpha[l];
+        }
+        double g;
+        if (!cov) g = -((a.bmag * ed - mkv / reg + mix) / K);
+        else g = -((a.bmag * ed - 1.0 / reg + mix) / (2 * K));
+        const int64_t gi = (cov ? fk : 0) + col * K + k;
+        RR_DEV_ASSERT(gi >= 0 && gi < 2 * fk);
+        const bool lg = a.islog[gi] != 0;
+        if (lg) g *= cov ? Ck : mkv;
+        n2 += g * g;
+        double s1 = a.s1[gi], s2 = a.s2[gi];
+        const double zn = sw_update(a, a.z[gi], g, a.lower[gi], a.upper[gi], s1, s2);
+        a.s1[gi] = s1;
+        a.s2[gi] = s2;
+        a.z[gi] = zn;
+        a.xout[gi] = lg ? exp(zn) : zn;
+    }
+    n2 = sw_block_sum(n2, red);
+    if (tid == 0) a.n2p[(size_t)ii * K + k] = n2;
+    if (!rff) return;
+    // the item's share of -(EdPhi o dPhi_i).sum() of this component: W[i, :] . T[i, :] (the factor 1 / l_i^2 in kernel D) with
+    // T = X^T (E_s o P_c - E_c o P_s), EdPhi[r][j] = (mk[j] D_r + sk[j] Q[r][j]) / (L K); the isotropic parameter takes input
+    // dimension 0 only, as the reference does (basis_functions.py:896)
+    const double sc = 1.0 / ((double)L * K);
+    for (int o = tid; o < M * cnt; o += SW_THREADS) {
+        const int r = o / cnt, j = o % cnt, js = cnt + j;
+        const double epc = (mk[j] * Dr[r] + sk[j] * Q[r * w + j]) * sc;
+        const double eps = (mk[js] * Dr[r] + sk[js] * Q[r * w + js]) * sc;
+        T[o] = eps * Phi[r * wp + j] - epc * Phi[r * wp + js];
+    }
+    __syncthreads();
+    for (int i = wave; i < c.n_ls; i += SW_WAVES) {
+        RR_DEV_ASSERT(i < c.d && c.ls0 + i < a.n_ls && i < a.maxls);
+        double acc = 0.0;
+        for (int o = lane; o < M * cnt; o += 64) {
+            const int r = o / cnt, j = o % cnt;
+            acc = fma(Wl[i * cnt + j] * Xb[r * c.d + i], T[o], acc);
+        }
+        acc = sw_wave_sum(acc);
+        if (lane == 0) a.glsp[((size_t)ii * K + k) * a.maxls + i] = acc;
+    }
+}
+
+// ---- D ------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_d_kernel(const SwArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double qm[SW_MAXK * SW_MAXK], logzm[SW_MAXK], llm[SW_MAXK], Rcm[SW_MAXCHILD], glsm[SW_MAXCHILD * SW_MAXD], redm[8];
+    ldsd *q = (ldsd *)qm, *logz = (ldsd *)logzm, *llk = (ldsd *)llm, *Rc = (ldsd *)Rcm, *gls = (ldsd *)glsm, *red = (ldsd *)redm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, K = a.K, F = a.F, L = a.L, M = a.M, nk = a.nkids, ns = a.ns;
+    const int64_t fk = (int64_t)F * K;
+    const double *xs = a.xin + 2 * fk;
+    RR_DEV_ASSERT(K <= SW_MAXK && nk <= SW_MAXCHILD && a.n_ls <= SW_MAXCHILD * SW_MAXD && ns == nk + a.n_lik + a.n_ls);
+    for (int o = tid; o < K * K; o += SW_THREADS) q[o] = a.qf[o];
+    if (tid < K) {   // sum of the log-likelihood terms of component tid (Gaussian: of the squared errors), block by block
+        double acc = 0.0;
+        for (int bx = 0; bx < a.nbx; ++bx) acc += a.llp[(size_t)tid * a.nbx + bx];
+        llk[tid] = acc;
+    } else if (tid >= 64 && tid < 64 + nk) {
+        double acc = 0.0;
+        for (int j = 0; j < K; ++j) acc += a.Rk[(tid - 64) * K + j];
+        Rc[tid - 64] = acc;
+    }
+    __syncthreads();
+    sw_logz(a, q, logz);
+    // the batch's f-independent part of loglike per latent sample (the log-factorial terms)
+    double lc = 0.0;
+    if (tid < M && a.lconst) {
+        const int64_t row = a.idx[tid];
+        RR_DEV_ASSERT(row >= 0 && row < a.N);
+        lc = a.lconst[row];
+    }
+    lc = sw_block_sum(lc, red);
+    double n2 = 0.0;
+    if (!a.objective_only) {
+        // the length scales' contractions: per slot the (item, component) partials of its child, one wave per slot
+        for (int h = wave; h < a.n_ls; h += SW_WAVES) {
+            int ci = 0;
+            while (ci + 1 < nk && !(h >= a.kid[ci].ls0 && h < a.kid[ci].ls0 + a.kid[ci].n_ls)) ++ci;
+            const SwChild &c = a.kid[ci];
+            const int i = h - c.ls0;
+            RR_DEV_ASSERT(i >= 0 && i < c.n_ls && i < a.maxls && c.item0 >= 0 && c.item0 + c.nitems <= a.nitems);
+            double acc = 0.0;
+            for (int e = lane; e < K * c.nitems; e += 64)
+                acc += a.glsp[((size_t)(c.item0 + e % c.nitems) * K + e / c.nitems) * a.maxls + i];
+            acc = sw_wave_sum(acc);
+            if (lane == 0) gls[h] = acc;
+        }
+        for (int e = tid; e < a.nitems * K; e += SW_THREADS) n2 += a.n2p[e];
+        n2 = sw_block_sum(n2, red);
+    }
+    __syncthreads();
+    double n2s = 0.0;
+    if (!a.objective_only) {
+        for (int p = tid; p < ns; p += SW_THREADS) {
+            double g;
+            if (p < nk) {  // dreg of the child's slice (glm.py:265-268)
+                const double iL = 1.0 / xs[p];
+                g = -(0.5 * (Rc[p] * (iL * iL) / K - (double)a.kid[p].width * iL));
+            } else if (p < nk + a.n_lik) {  // Gaussian variance (likelihoods.py:370-396)
+                const double iv = 1.0 / xs[p];
+                double sm2 = 0.0;
+                for (int j = 0; j < K; ++j) sm2 += 0.5 * (llk[j] * iv * iv - iv * (double)M * L) / L;
+                g = 0.0 - sm2 / K;
+            } else {
+                const double l = xs[p];
+                g = gls[p - nk - a.n_lik] / (1.0 * (l * l));
+            }
+            const int64_t gi = 2 * fk + p;
+            const bool lg = a.islog[gi] != 0;
+            if (lg) g *= xs[p];
+            n2s += g * g;
+            double s1 = a.s1[gi], s2 = a.s2[gi];
+            const double zn = sw_update(a, a.z[gi], g, a.lower[gi], a.upper[gi], s1, s2);
+            a.s1[gi] = s1;
+            a.s2[gi] = s2;
+            a.z[gi] = zn;
+            a.xout[gi] = lg ? exp(zn) : zn;
+        }
+        n2s = sw_block_sum(n2s, red);
+    }
+    if (wave == 0) {   // the record: |g| (sgd.py:399) and -ELBO (glm.py:285-292)
+        double ell = 0.0, part = 0.0;
+        const double ivar = a.n_lik ? 1.0 / xs[nk] : 0.0;
+        for (int j = lane; j < K; j += 64) ell += (a.n_lik ? -0.5 * llk[j] * ivar : llk[j]) / L;
+        double llc = lc;
+        if (a.n_lik) llc = -0.5 * log(2.0 * 3.141592653589793 * xs[nk]) * (double)M;
+        ell = sw_wave_sum(ell) + llc * K;
+        for (int ci = lane; ci < nk; ci += 64) {
+            const double reg = xs[ci];
+            part += -0.5 * K * ((double)a.kid[ci].width * log(reg)) - 0.5 * (Rc[ci] / reg);
+        }
+        for (int j = lane; j < K; j += 64) part -= logz[j];
+        part = sw_wave_sum(part);
+        const double elbo = (ell * a.bmag - 0.5 * F * K * 1.8378770664093453 + part + log((double)K)) / K;
+        if (lane == 0) {
+            *a.obj = -elbo;
+            if (a.norm) *a.norm = sqrt(n2 + n2s);
+        }
+    }
+}
+
+// x = from_log(z) of every coordinate (create, set_start: not part of a step)
+__global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_x_kernel(const double *z, const unsigned char *islog, double *x, int64_t np) {
+    const int64_t p = (int64_t)blockIdx.x * SW_THREADS + threadIdx.x;
+    if (p < np) x[p] = islog[p] ? exp(z[p]) : z[p];
+}
+
+// ---- the one place that decides the split -------------------------------------------------------------------------------
+// width: the largest count of frequencies <= SW_ITEM_DEFAULT (RR_SVIW_ITEM replaces that cap) whose item fits the LDS budget for
+// every random Fourier child; a linear child is one item whatever its width.  Returns the number of items, or -1 when an item
+// cannot fit (or a child is of another kind); items (cap triples) may be null.
+static int sw_plan(int n_children, const int *kind, const int *n, const int *d, int K, int L, int M, int cap, int *items, int64_t info[4]) {
+    int want = SW_ITEM_DEFAULT;
+    const char *env = getenv("RR_SVIW_ITEM");
+    if (env && atoi(env) >= 1) want = atoi(env);
+    int width = want;
+    size_t worst = 0;
+    for (int c = 0; c < n_children; ++c) {
+        if (kind[c] == RR_SGD_CHILD_RFF) {
+            if (n[c] < 1 || d[c] < 1) return -1;
+            int wc = std::min(width, n[c]);
+            while (wc >= 1 && sw_item_bytes(1, wc, d[c], K, L, M) > SW_LDS_BUDGET) --wc;
+            if (wc < 1) return -1;
+            if (wc < std::min(width, n[c])) width = wc;
+        } else if (kind[c] == RR_SGD_CHILD_LINEAR) {
+            if (n[c] < 1 || sw_item_bytes(0, n[c], d[c], K, L, M) > SW_LDS_BUDGET) return -1;
+        } else {
+            return -1;
+        }
+    }
+    int ni = 0;
+    for (int c = 0; c < n_children; ++c) {
+        const bool rff = kind[c] == RR_SGD_CHILD_RFF;
+        for (int j0 = 0; j0 < n[c]; j0 += rff ? width : n[c]) {
+            const int cnt = rff ? std::min(width, n[c] - j0) : n[c];
+            worst = std::max(worst, sw_item_bytes(rff, cnt, d[c], K, L, M));
+            if (items && ni < cap) {
+                items[3 * ni] = c;
+                items[3 * ni + 1] = j0;
+                items[3 * ni + 2] = cnt;
+            }
+            ++ni;
+        }
+    }
+    if (info) {
+        info[0] = ni;
+        info[1] = width;
+        info[2] = (int64_t)worst;
+        info[3] = SW_LDS_BUDGET;
+    }
+    return ni;
+}
+
+}  // namespace
+
+struct rr_glm_sviw {
+    rr_ctx *ctx = nullptr;
+    SwArgs a;
+    SwChild hkid[SW_MAXCHILD];
+    SwChild *dkid = nullptr;
+    SwItem *ditems = nullptr;
+    std::vector<double *> dW;
+    unsigned char *islog = nullptr;
+    double *lower = nullptr, *upper = nullptr, *xbuf[2] = {nullptr, nullptr}, *objs = nullptr, *norms = nullptr;
+    int64_t maxiter = 0, t = 0;
+    size_t lds_bytes = 0;
+    double *cand = nullptr, *out = nullptr;
+    size_t cand_cap = 0, out_cap = 0;
+};
+
+static void sw_free(rr_glm_sviw *o) {
+    void *q[] = {o->dkid, o->ditems, o->a.z, o->a.s1, o->a.s2, o->lower, o->upper, o->islog, o->xbuf[0], o->xbuf[1], o->objs, o->norms,
+                 o->a.Phi, o->a.fsp, o->a.qp, o->a.Rp, o->a.dfs, o->a.llp, o->a.qf, o->a.Rk, o->a.n2p, o->a.glsp, o->cand, o->out};
+    for (void *v : q)
+        if (v) (void)hipFree(v);
+    for (double *w : o->dW)
+        if (w) (void)hipFree(w);
+    delete o;
+}
+
+static void sw_form_x(rr_glm_sviw *o) {
+    const int64_t np = o->a.np;
+    hipLaunchKernelGGL(rr_glm_sviw_x_kernel, dim3((unsigned)((np + SW_THREADS - 1) / SW_THREADS)), dim3(SW_THREADS), 0, o->ctx->stream,
+                       (const double *)o->a.z, (const unsigned char *)o->islog, o->xbuf[o->t & 1], np);
+}
+
+extern "C" {
+
+int rr_glm_sviw_supported(int F, int K, int L, int M, int n_children, int dsum, int n_ls) {
+    if (F < 1 || F > SW_MAXF || K < 1 || K > SW_MAXK || L < 1 || L > SW_MAXL || M < 1 || M > SW_MAXM) return 0;
+    if (n_children < 1 || n_children > SW_MAXCHILD || F < n_children || dsum < 0 || dsum > SW_MAXCHILD * SW_MAXD) return 0;
+    if (n_ls < 0 || n_ls > SW_MAXCHILD * SW_MAXD) return 0;
+    // the widest child the inputs allow: one random Fourier child and one linear child over min(dsum, 128) columns must both fit
+    const int d = std::max(1, std::min(dsum, SW_MAXD));
+    const int kind[2] = {RR_SGD_CHILD_RFF, RR_SGD_CHILD_LINEAR}, n[2] = {std::max(1, F / 2), std::min(F, d + 1)}, dd[2] = {d, d};
+    int64_t info[4];
+    if (sw_plan(2, kind, n, dd, K, L, M, 0, nullptr, info) < 1) return 0;
+    // the partials of fs: (items, K, L, M) doubles
+    const int64_t items = (F / 2 + info[1] - 1) / info[1] + n_children;
+    if (items * K * L * M * 8 > SW_SCRATCH_MAX) return 0;
+    // The upper edge in minibatch x F, from the measured per-step times (docs/KERNELS.md 3.48: MI355X, K L = 500, d = 21, F = 512
+    // ... 16384, minibatches of 10, 32 and 64 rows): the chain costs ~55 + 0.005 F + 7.4e-4 M F (K L / 500) us, the step-per-call
+    // loop ~150 + 0.025 F us whatever the minibatch.  In range is what the chain wins by 1.25 x on that model: every measured
+    // shape inside won by 2.2 x or more, the two that won by 1.2 x (64 rows at F = 2048, 32 at F = 16384) and the one that lost
+    // (64 at F = 16384) are outside.  Nothing routes to a slower loop.
+    const double wide_us = 55.0 + 0.005 * F + 7.4e-4 * (double)M * F * ((double)K * L / 500.0);
+    const double step_us = 150.0 + 0.025 * F;
+    return 1.25 * wide_us <= step_us ? 1 : 0;
+}
+
+int rr_glm_sviw_plan(int n_children, const int *kind, const int *n, const int *d, int K, int L, int M, int cap, int *items,
+                     int64_t info[4]) {
+    RR_REQUIRE(kind != nullptr && n != nullptr && d != nullptr && info != nullptr && n_children >= 1 && n_children <= SW_MAXCHILD &&
+               K >= 1 && K <= SW_MAXK && L >= 1 && M >= 1 && cap >= 0, "rr_glm_sviw_plan: bad argument");
+    for (int c = 0; c < n_children; ++c)
+        RR_REQUIRE(kind[c] == RR_SGD_CHILD_RFF || kind[c] == RR_SGD_CHILD_LINEAR, "rr_glm_sviw_plan: child %d: kind %d is not taken by "
+                   "the wide loop (random Fourier and linear children only)", c, kind[c]);
+    if (sw_plan(n_children, kind, n, d, K, L, M, cap, items, info) < 1) {
+        rr_set_error("rr_glm_sviw_plan: no item of this shape fits %d bytes of LDS (K = %d, nsamples = %d, minibatch = %d)",
+                     SW_LDS_BUDGET, K, L, M);
+        return RR_ERR_UNSUPPORTED;
+    }
+    return RR_OK;
+}
+
+int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                       const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K, int L,
+                       int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper, const unsigned char *is_log,
+                       int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_sviw **out) {
+    const char *who = "rr_glm_sviw_create";
+    RR_REQUIRE(ctx != nullptr && children != nullptr && dX != nullptr && x_dtype != nullptr && ldx != nullptr && dy != nullptr &&
+               z0 != nullptr && lower != nullptr && upper != nullptr && is_log != nullptr && upd_par != nullptr && out != nullptr,
+               "%s: null argument", who);
+    *out = nullptr;
+    RR_REQUIRE(n_children >= 1 && n_children <= SW_MAXCHILD, "%s: 1 <= children <= %d", who, SW_MAXCHILD);
+    RR_REQUIRE(K >= 1 && K <= SW_MAXK && L >= 1 && M >= 1 && N >= 1, "%s: bad K, L, minibatch or N", who);
+    RR_REQUIRE(lik >= RR_LIK_BERNOULLI && lik <= RR_LIK_POISSON_SOFTPLUS && (lik == RR_LIK_GAUSSIAN) == (n_lik == 1),
+               "%s: likelihood %d with %d likelihood parameter(s)", who, lik, n_lik);
+    RR_REQUIRE((lik == RR_LIK_BINOMIAL) == (drowarg != nullptr), "%s: the per-row argument goes with the binomial likelihood", who);
+    RR_REQUIRE(updater >= RR_UPD_SGD && updater <= RR_UPD_ADAM, "%s: unknown updater %d", who, updater);
+    RR_REQUIRE(maxiter >= 1 && maxiter < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), "%s: bad maxiter / N", who);
+    RR_REQUIRE(dtype == RR_F32 || dtype == RR_F64, "%s: bad dtype", who);
+    for (int s = 0; s < n_children; ++s)
+        RR_REQUIRE(children[s].kind == RR_SGD_CHILD_RFF || children[s].kind == RR_SGD_CHILD_LINEAR,
+                   "%s: child %d: kind %d is not taken by the wide loop (random Fourier and linear children only)", who, s, children[s].kind);
+    RR_CHECK_HIP(hipSetDevice(ctx->device));
+    rr_glm_sviw *o = new rr_glm_sviw();
+    o->ctx = ctx;
+    SwArgs &a = o->a;
+    memset(&a, 0, sizeof a);
+    memset(o->hkid, 0, sizeof o->hkid);
+    int col = 0, nls = 0, dsum = 0, maxls = 1;
+    int pk[SW_MAXCHILD], pn[SW_MAXCHILD], pd[SW_MAXCHILD];
+    for (int s = 0; s < n_children; ++s) {
+        const rr_glm_sgd_child &k = children[s];
+        SwChild &c = o->hkid[s];
+        c.kind = k.kind;
+        c.col0 = col;
+        c.ls0 = nls;
+        c.X = dX[s];
+        c.ldx = ldx[s];
+        c.x_f64 = x_dtype[s] == RR_F64;
+        bool ok = dX[s] != nullptr && (x_dtype[s] == RR_F32 || x_dtype[s] == RR_F64);
+        if (ok && k.kind == RR_SGD_CHILD_RFF) {
+            rr_basis *b = k.basis;
+            ok = b != nullptr && b->kind == RR_KIND_RFF && b->ctx == ctx && b->d >= 1 && b->d <= SW_MAXD && b->n >= 1 &&
+                 (k.n_ls == 1 || k.n_ls == b->d) && (int)b->W.size() == b->d * b->n;
+            if (ok) {
+                c.d = b->d; c.n = b->n; c.n_ls = k.n_ls; c.width = 2 * b->n; c.onescol = 0;
+                double *w = nullptr;
+                if (hipMalloc((void **)&w, b->W.size() * 8) != hipSuccess ||
+                    hipMemcpy(w, b->W.data(), b->W.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+                    (void)hipGetLastError();
+                    if (w) (void)hipFree(w);
+                    sw_free(o);
+                    rr_set_error("%s: device allocation failed", who);
+                    return RR_ERR_OOM;
+                }
+                o->dW.push_back(w);
+                c.W = w;
+                pn[s] = c.n;
+            }
+        } else if (ok) {
+            ok = k.d >= 1 && k.d <= SW_MAXD && k.n_ls == 0;
+            c.d = k.d; c.n = 0; c.n_ls = 0; c.onescol = k.onescol ? 1 : 0; c.width = k.d + c.onescol;
+            pn[s] = c.width;
+        }
+        if (!ok) {
+            sw_free(o);
+            rr_set_error("%s: child %d: a random Fourier basis of this context with Xdim <= %d and 1 or Xdim length scales, or a "
+                         "linear child with 1 <= d <= %d columns, and its resident rows", who, s, SW_MAXD, SW_MAXD);
+            return RR_ERR_INVALID;
+        }
+        pk[s] = c.kind;
+        pd[s] = c.d;
+        maxls = std::max(maxls, c.n_ls);
+        col += c.width;
+        nls += c.n_ls;
+        dsum += c.d;
+    }
+    a.nkids = n_children; a.F = col; a.K = K; a.L = L; a.M = M; a.lik = lik; a.n_lik = n_lik; a.n_ls = nls; a.maxls = maxls;
+    a.ns = n_children + n_lik + nls; a.updater = updater; a.y_f64 = dtype == RR_F64; a.N = N;
+    a.np = 2 * (int64_t)col * K + a.ns;
+    a.y = dy; a.rowarg = drowarg; a.lconst = dlconst; a.bmag = bmag;
+    a.nbx = (L * M + SW_THREADS - 1) / SW_THREADS;
+    for (int i = 0; i < 4; ++i) a.up[i] = upd_par[i];
+    int64_t info[4] = {0, 0, 0, 0};
+    const int ni = rr_glm_sviw_supported(a.F, K, L, M, n_children, dsum, nls) ? sw_plan(n_children, pk, pn, pd, K, L, M, 0, nullptr, info) : -1;
+    if (ni < 1 || (int64_t)ni * K * L * M * 8 > 2 * SW_SCRATCH_MAX) {
+        sw_free(o);
+        rr_set_error("%s: F = %d, K = %d, nsamples = %d, minibatch = %d is outside the wide small-batch loop's range "
+                     "(rr_glm_sviw_supported)", who, a.F, K, L, M);
+        return RR_ERR_UNSUPPORTED;
+    }
+    std::vector<int> items((size_t)3 * ni);
+    (void)sw_plan(n_children, pk, pn, pd, K, L, M, ni, items.data(), info);
+    std::vector<SwItem> hitems((size_t)ni);
+    for (int s = 0; s < n_children; ++s) o->hkid[s].item0 = -1;
+    for (int i = 0; i < ni; ++i) {
+        hitems[i].child = items[3 * i];
+        hitems[i].j0 = items[3 * i + 1];
+        hitems[i].cnt = items[3 * i + 2];
+        SwChild &c = o->hkid[hitems[i].child];
+        if (c.item0 < 0) c.item0 = i;
+        c.nitems = i - c.item0 + 1;
+    }
+    a.nitems = ni;
+    o->lds_bytes = (size_t)info[2];
+    o->maxiter = maxiter;
+    const size_t nb = (size_t)a.np * 8, nik = (size_t)ni * K;
+    hipError_t e = hipMalloc((void **)&a.z, nb);
+    if (e == hipSuccess) e = hipMalloc((void **)&o->dkid, sizeof(o->hkid));
+    if (e == hipSuccess) e = hipMemcpy(o->dkid, o->hkid, sizeof(o->hkid), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&o->ditems, (size_t)ni * sizeof(SwItem));
+    if (e == hipSuccess) e = hipMemcpy(o->ditems, hitems.data(), (size_t)ni * sizeof(SwItem), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.s1, nb);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.s2, nb);
+    if (e == hipSuccess) e = hipMalloc((void **)&o->lower, nb);
+    if (e == hipSuccess) e = hipMalloc((void **)&o->upper, nb);
+    if (e == hipSuccess) e = hipMalloc((void **)&o->islog, (size_t)a.np);
+    if (e == hipSuccess) e = hipMalloc((void **)&o->xbuf[0], nb);
+    if (e == hipSuccess) e = hipMalloc((void **)&o->xbuf[1], nb);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.Phi, (size_t)M * a.F * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.fsp, nik * L * M * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.qp, nik * K * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.Rp, nik * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.dfs, (size_t)K * L * M * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.llp, (size_t)K * a.nbx * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.qf, (size_t)K * K * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.Rk, (size_t)n_children * K * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.n2p, nik * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&a.glsp, nik * maxls * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&o->objs, (size_t)maxiter * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&o->norms, (size_t)maxiter * 8);
+    if (e == hipSuccess) e = hipMemcpy(a.z, z0, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->lower, lower, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->upper, upper, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->islog, is_log, (size_t)a.np, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(a.s1, 0, nb);
+    if (e == hipSuccess) e = hipMemset(a.s2, 0, nb);
+    if (e == hipSuccess) e = hipMemset(a.glsp, 0, nik * maxls * 8);
+    if (e == hipSuccess) e = hipMemset(o->objs, 0, (size_t)maxiter * 8);
+    if (e == hipSuccess) e = hipMemset(o->norms, 0, (size_t)maxiter * 8);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)rr_glm_sviw_a_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)rr_glm_sviw_c_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        sw_free(o);
+        rr_set_error("%s: %s", who, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP;
+    }
+    a.lower = o->lower; a.upper = o->upper; a.islog = o->islog; a.kid = o->dkid; a.items = o->ditems;
+    sw_form_x(o);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        sw_free(o);
+        rr_set_error("%s: %s", who, hipGetErrorString(e));
+        return RR_ERR_HIP;
+    }
+    *out = o;
+    return RR_OK;
+}
+
+int rr_glm_sviw_set_start(rr_glm_sviw *o, const double *z0, const double *lower, const double *upper, const unsigned char *is_log) {
+    RR_REQUIRE(o != nullptr && o->t == 0, "rr_glm_sviw_set_start: before the first step only");
+    RR_CHECK_HIP(hipSetDevice(o->ctx->device));
+    RR_CHECK_HIP(hipStreamSynchronize(o->ctx->stream));
+    const size_t nb = (size_t)o->a.np * 8;
+    if (z0) RR_CHECK_HIP(hipMemcpy(o->a.z, z0, nb, hipMemcpyHostToDevice));
+    if (lower) RR_CHECK_HIP(hipMemcpy(o->lower, lower, nb, hipMemcpyHostToDevice));
+    if (upper) RR_CHECK_HIP(hipMemcpy(o->upper, upper, nb, hipMemcpyHostToDevice));
+    if (is_log) RR_CHECK_HIP(hipMemcpy(o->islog, is_log, (size_t)o->a.np, hipMemcpyHostToDevice));
+    sw_form_x(o);
+    RR_CHECK_HIP(hipGetLastError());
+    return RR_OK;
+}
+
+int rr_glm_sviw_run(rr_glm_sviw *o, int64_t steps, const int *d_idx, const float *dE, uint64_t seed, uint64_t key0) {
+    RR_REQUIRE(o != nullptr && d_idx != nullptr && steps >= 1 && steps <= (1 << 20), "rr_glm_sviw_run: 1 <= steps <= 2^20 per call");
+    RR_REQUIRE(o->t + steps <= o->maxiter, "rr_glm_sviw_run: %lld steps done, %lld more asked, %lld at most", (long long)o->t,
+               (long long)steps, (long long)o->maxiter);
+    rr_ctx *c = o->ctx;
+    RR_CHECK_HIP(hipSetDevice(c->device));
+    SwArgs a = o->a;
+    const dim3 gi((unsigned)a.nitems, (unsigned)a.K), gb((unsigned)a.nbx, (unsigned)a.K), th(SW_THREADS);
+    for (int64_t t = 0; t < steps; ++t) {
+        const int64_t gt = o->t + t;
+        a.idx = d_idx + (size_t)t * a.M;
+        a.E = dE ? dE + (size_t)t * a.K * a.L * a.F : nullptr;
+        // the key of rr_glm_draw_kernel for (seed, key0 + t); Adam's bias (sgd.py:322-323): nothing of either on the device
+        uint64_t x = (seed ^ ((key0 + (uint64_t)t) * 0xD1B54A32D192ED03ull)) + 0x9E3779B97F4A7C15ull;
+        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+        a.stepkey = x ^ (x >> 31);
+        a.b1t = 1.0 - pow(a.up[1], (double)(gt + 1));
+        a.b2t = 1.0 - pow(a.up[2], (double)(gt + 1));
+        a.xin = o->xbuf[gt & 1];
+        a.xout = o->xbuf[(gt + 1) & 1];
+        a.obj = o->objs + gt;
+        a.norm = o->norms + gt;
+        a.objective_only = 0;
+        hipLaunchKernelGGL(rr_glm_sviw_a_kernel, gi, th, o->lds_bytes, c->stream, a);
+        hipLaunchKernelGGL(rr_glm_sviw_b_kernel, gb, th, 0, c->stream, a);
+        hipLaunchKernelGGL(rr_glm_sviw_c_kernel, gi, th, o->lds_bytes, c->stream, a);
+        hipLaunchKernelGGL(rr_glm_sviw_d_kernel, dim3(1), th, 0, c->stream, a);
+    }
+    RR_CHECK_HIP(hipGetLastError());
+    o->t += steps;
+    return RR_OK;
+}
+
+int rr_glm_sviw_starts(rr_glm_sviw *o, int ncand, const int *d_idx, const double *cand_host, const float *dE, uint64_t seed,
+                       uint64_t key0, double *objs_host) {
+    RR_REQUIRE(o != nullptr && d_idx != nullptr && cand_host != nullptr && objs_host != nullptr && ncand >= 1 && ncand < (1 << 20),
+               "rr_glm_sviw_starts: bad argument");
+    rr_ctx *c = o->ctx;
+    RR_CHECK_HIP(hipSetDevice(c->device));
+    SwArgs a = o->a;
+    const size_t want = (size_t)ncand * a.np;
+    if (o->cand_cap < want || o->out_cap < (size_t)ncand) {
+        RR_CHECK_HIP(hipStreamSynchronize(c->stream));
+        if (o->cand) (void)hipFree(o->cand);
+        if (o->out) (void)hipFree(o->out);
+        o->cand = o->out = nullptr;
+        o->cand_cap = o->out_cap = 0;
+        RR_CHECK_HIP(hipMalloc((void **)&o->cand, want * 8));
+        RR_CHECK_HIP(hipMalloc((void **)&o->out, (size_t)ncand * 8));
+        o->cand_cap = want;
+        o->out_cap = (size_t)ncand;
+    }
+    RR_CHECK_HIP(hipMemcpyAsync(o->cand, cand_host, want * 8, hipMemcpyHostToDevice, c->stream));
+    const dim3 gi((unsigned)a.nitems, (unsigned)a.K), gb((unsigned)a.nbx, (unsigned)a.K), th(SW_THREADS);
+    for (int s = 0; s < ncand; ++s) {
+        a.idx = d_idx + (size_t)s * a.M;
+        a.E = dE ? dE + (size_t)s * a.K * a.L * a.F : nullptr;
+        uint64_t x = (seed ^ ((key0 + (uint64_t)s) * 0xD1B54A32D192ED03ull)) + 0x9E3779B97F4A7C15ull;
+        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+        a.stepkey = x ^ (x >> 31);
+        a.xin = o->cand + (size_t)s * a.np;
+        a.xout = nullptr;
+        a.obj = o->out + s;
+        a.norm = nullptr;
+        a.objective_only = 1;
+        hipLaunchKernelGGL(rr_glm_sviw_a_kernel, gi, th, o->lds_bytes, c->stream, a);
+        hipLaunchKernelGGL(rr_glm_sviw_b_kernel, gb, th, 0, c->stream, a);
+        hipLaunchKernelGGL(rr_glm_sviw_d_kernel, dim3(1), th, 0, c->stream, a);
+    }
+    RR_CHECK_HIP(hipGetLastError());
+    RR_CHECK_HIP(hipMemcpyAsync(objs_host, o->out, (size_t)ncand * 8, hipMemcpyDeviceToHost, c->stream));
+    RR_CHECK_HIP(hipStreamSynchronize(c->stream));
+    return RR_OK;
+}
+
+int rr_glm_sviw_read(rr_glm_sviw *o, double *z, double *objs, double *norms, int64_t *steps) {
+    RR_REQUIRE(o != nullptr, "rr_glm_sviw_read: null argument");
+    rr_ctx *c = o->ctx;
+    RR_CHECK_HIP(hipSetDevice(c->device));
+    RR_CHECK_HIP(hipStreamSynchronize(c->stream));
+    if (z) RR_CHECK_HIP(hipMemcpy(z, o->a.z, (size_t)o->a.np * 8, hipMemcpyDeviceToHost));
+    if (objs && o->t) RR_CHECK_HIP(hipMemcpy(objs, o->objs, (size_t)o->t * 8, hipMemcpyDeviceToHost));
+    if (norms && o->t) RR_CHECK_HIP(hipMemcpy(norms, o->norms, (size_t)o->t * 8, hipMemcpyDeviceToHost));
+    if (steps) *steps = o->t;
+    return RR_OK;
+}
+
+void rr_glm_sviw_destroy(rr_glm_sviw *o) {
+    if (!o) return;
+    (void)hipSetDevice(o->ctx->device);
+    (void)hipStreamSynchronize(o->ctx->stream);
+    sw_free(o);
+}
+
+}  // extern "C"

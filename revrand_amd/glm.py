@@ -165,11 +165,24 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         stages of the f32 pipeline (draws, uploads and gathers made a step ahead on worker threads) are left out in this mode:
         batch, draws and step follow each other on the calling thread, in the reference's order.  Refused with ValueError at
         ``fit``, before any device call: ``sampler="device"``, ``devices=``, ``distributed=True``, ``predict_engine="device"``,
-        a split ``gram_engine`` and ``fused_bases`` other than "fourier".  Any other value of ``dtype``: ValueError at ``fit``."""
+        a split ``gram_engine``, ``fused_bases`` other than "fourier" and ``wide_fused=True``.  Any other value of ``dtype``:
+        ValueError at ``fit``.
+    wide_fused : False (default) | True
+        The small-minibatch loop for WIDE bases.  ``fused_bases`` describes the many-steps-per-launch kernel, which holds a
+        component's whole state in one compute unit's LDS: minibatch x D <= 8192, so at 10 rows everything above D ~ 800 is
+        declined and takes the step-per-call loop (one library call and ~31 dependent launches per step).  True: such a shape,
+        when every child is a random Fourier, FastFoodRBF or linear child and rr_glm_sviw_supported takes it (K <= 32, nsamples
+        <= 128, minibatch <= 64, D <= 32768), runs on a fixed chain of four kernels per step with many steps queued per library
+        call (rr_svi_wide.hip) -- the same minibatches, draws (either sampler), updaters and likelihoods, float64 throughout,
+        bitwise reproducible.  A shape the LDS kernel takes still takes it; any other child, several ranks or minibatches split
+        over ``devices=`` keep the step-per-call loop (``fused_bases`` keeps its meaning for the LDS kernel only).  The random
+        starts are scored in chunks whose uploads stay within the loop's block size.  False: every fit takes the loop it always
+        took.  Any other value: ValueError at ``fit``, before any device call."""
 
     def __init__(self, likelihood=Gaussian(), basis=LinearBasis(), K=10, maxiter=3000, batch_size=10, updater=None,
                  nsamples=50, nstarts=500, random_state=None, sampler="host", distributed=False, gram_engine=None,
-                 devices=None, predict_engine="host", resident_bases="fourier", fused_bases="fourier", dtype="f32"):
+                 devices=None, predict_engine="host", resident_bases="fourier", fused_bases="fourier", dtype="f32",
+                 wide_fused=False):
         self.likelihood = likelihood
         self.basis = basis
         self.K = K
@@ -187,6 +200,7 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         self.resident_bases = resident_bases
         self.fused_bases = fused_bases
         self.dtype = dtype
+        self.wide_fused = wide_fused
         self.random_ = check_random_state(self.random_state)
 
     def fit(self, X, y, likelihood_args=()):
@@ -203,6 +217,9 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         dtype = getattr(self, "dtype", "f32")
         if dtype not in ("f32", "f64"):
             raise ValueError("dtype must be 'f32' or 'f64'")
+        wide = getattr(self, "wide_fused", False)
+        if not (wide is True or wide is False):
+            raise ValueError("wide_fused must be True or False")
         if dtype == "f32":
             return
         if self.sampler != "host":
@@ -217,6 +234,8 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
             raise ValueError("dtype='f64' has no split gram_engine (the float64 matrix has none)")
         if getattr(self, "fused_bases", "fourier") != "fourier":
             raise ValueError("dtype='f64' needs fused_bases='fourier' (the fused loop has its own float64 range)")
+        if wide:
+            raise ValueError("dtype='f64' does not run with wide_fused=True (the wide loop's draws are float32)")
 
     def _group(self):
         if getattr(self, "devices", None) is None:
@@ -368,6 +387,7 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
     _resident_sgd = True    # False (or RR_GLM_RESIDENT_SGD=0): always the host loop around `_elbo` (tests, A/B runs)
 
     _fused_sgd = True       # False (or RR_GLM_FUSED=0): never the many-steps-per-launch loop of small minibatches
+    _wide_fused_force = False   # True (tests): wide_fused=True sends shapes the LDS kernel would take to the wide loop too
 
     def _resident_loop(self, params, y=None, likelihood_args=()):
         """The SGD loop with parameters, updater state and gradient in device memory (`_ResidentLoop`, rr_glm_sgd) when this
@@ -500,8 +520,14 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
                         return _FusedLoop(self, feats, n_lik, children, y, likelihood_args, gm_children=True)
                 elif _hip.svi_supported_all(F, self.K, self.nsamples, M, len(children), dsum, n_ls, tables):
                     return _FusedLoop(self, feats, n_lik, children, y, likelihood_args, all_children=True)
-            elif _hip.svi_supported(F, self.K, self.nsamples, M, len(children), dsum, n_ls):
+            elif _hip.svi_supported(F, self.K, self.nsamples, M, len(children), dsum, n_ls) \
+                    and not (self._wide_fused_force and getattr(self, "wide_fused", False) is True):
                 return _FusedLoop(self, feats, n_lik, children, y, likelihood_args)
+            # wide bases (wide_fused=True): what the LDS kernel declines, on the chain of kernels of rr_svi_wide.hip
+            if getattr(self, "wide_fused", False) is True \
+                    and all(c[0] == "rff" or (c[0] == "linear" and c[1] <= 128) for c in children) \
+                    and _hip.sviw_supported(F, self.K, self.nsamples, M, len(children), dsum, n_ls):
+                return _FusedLoop(self, feats, n_lik, children, y, likelihood_args, wide=True)
         return _ResidentLoop(self, feats, n_lik, children, comm=comm)
 
     def _reference_draws(self, out=None):
@@ -1166,8 +1192,9 @@ class _FusedLoop(object):
     BLOCK_BYTES = 48 << 20    # draws uploaded per launch at most (two device buffers of this size in turn)
     BLOCK_STEPS = 256
 
-    def __init__(self, glm, feats, n_lik, children, y, likelihood_args, all_children=False, gm_children=False):
+    def __init__(self, glm, feats, n_lik, children, y, likelihood_args, all_children=False, gm_children=False, wide=False):
         from . import optimize as opt
+        self.wide = wide                   # rr_glm_sviw (rr_svi_wide.hip): the chain of kernels for wide bases
         self.glm, self.feats, self.n_lik, self.children = glm, feats, n_lik, children
         self.all_children = all_children   # rr_glm_svi_create_all: centre and polynomial children too
         self.gm_children = gm_children     # rr_glm_svi_create_gm: and spectral-mixture components
@@ -1210,7 +1237,7 @@ class _FusedLoop(object):
         F = int(g.D_)
         self.np_ = 2 * F * g.K + len(kids) + self.n_lik + sum(c[2] for c in self.children if c[0] in ("rff", "gm", "centres"))
         hold = np.zeros(self.np_)
-        self.svi = _hip.FusedSvi(dev, kids, len(self.y), self.dy, self.dn, self.dlc, g.K, g.nsamples, self.M, lik, self.n_lik, hold,
+        self.svi = (_hip.WideSvi if self.wide else _hip.FusedSvi)(dev, kids, len(self.y), self.dy, self.dn, self.dlc, g.K, g.nsamples, self.M, lik, self.n_lik, hold,
                                  np.full(self.np_, -np.inf), np.full(self.np_, np.inf), np.zeros(self.np_, dtype=np.uint8),
                                  _hip.UPDATER_IDS[kind], par, max(1, int(g.maxiter)), g.B_, all_children=self.all_children,
                                  gm_children=self.gm_children)
@@ -1256,10 +1283,27 @@ class _FusedLoop(object):
             self._start_draws.append(g._reference_draws())
 
     def score_starts(self):
-        """-ELBO of every noted candidate, in order: one launch."""
+        """-ELBO of every noted candidate, in order: one launch (the wide loop: in chunks whose uploads stay within
+        BLOCK_BYTES -- at D = 16384 one candidate's draws are 32 MB; the objectives are concatenated in order)."""
         g = self.glm
         svi = self._ensure()
         ns = len(self._cands)
+        if self.wide:
+            per = self._cands[0].nbytes + (self._start_draws[0].nbytes if g.sampler != "device" else 0)
+            chunk = int(max(1, min(ns, self.BLOCK_BYTES // max(per, 1))))
+            objs = []
+            for lo in range(0, ns, chunk):
+                hi = min(ns, lo + chunk)
+                didx = self._up("sidx", np.stack(self._start_idx[lo:hi]))
+                if g.sampler == "device":
+                    objs.append(svi.starts(didx, np.stack(self._cands[lo:hi]), None, g._dev_seed, g._dev_step))
+                    g._dev_step += hi - lo
+                else:
+                    objs.append(svi.starts(didx, np.stack(self._cands[lo:hi]), self._up("sE", np.stack(self._start_draws[lo:hi]))))
+            g._iteration(advance=ns)
+            self._cands, self._start_idx, self._start_draws = [], [], []
+            self._bufs.pop("sE").free() if "sE" in self._bufs else None
+            return np.concatenate(objs)
         didx = self._up("sidx", np.stack(self._start_idx))
         if g.sampler == "device":
             objs = svi.starts(didx, np.stack(self._cands), None, g._dev_seed, g._dev_step)
