@@ -377,6 +377,27 @@ int rr_featmat64_glm_centres(rr_featmat64 *fm, rr_basis *basis, const void *dX, 
                              double *dg);
 int rr_featmat64_glm_edphi(rr_featmat64 *fm, int64_t col0, int64_t ncols, double *E);
 int rr_featmat64_project(rr_featmat64 *fm, const double *W, int S, double *out);
+/* ---- FastFoodRBF / FastFoodGM children of the float64 matrix (docs/KERNELS.md 3.49) ------------------------------------------
+ * rr_featmat64_put_fastfood / _put_fastfood_gm: rr_featmat_put_fastfood / _put_fastfood_gm into the float64 matrix -- the chain
+ * kernels' FLOAT64 instances whatever the handle's compute (every handle carries float64 tables), device X float32 or float64
+ * with ldx >= d, any col0; columns outside the block and the matrix' padding are left alone.  put_fastfood serves handles of
+ * rr_fastfood_create and rr_fastfood_create_wide[_gm]; put_fastfood_gm (4n columns: [cos | sin](VX + mX) at col0, [cos | sin](VX - mX)
+ * at col0 + 2n) has rr_featmat_put_fastfood_gm's range: 16 <= d2 <= 256 on a plain handle, 512 .. 4096 on a
+ * rr_fastfood_create_wide_gm handle, RR_ERR_UNSUPPORTED otherwise (before any column is claimed).
+ * rr_featmat64_pass2_xt / _glm_xt: dT (d, n) += X^T A (DEVICE float64) for the trig block pair [cos | sin] at [col0, col0 + 2n),
+ * A as rr_featmat64_pass2_rff / _glm_rff contract it, for rows of 1 <= d <= RR_FEATMAT64_XT_MAX_DIM columns and WITHOUT a random
+ * Fourier handle.  d <= 128: the _rff functions' kernel, grid and determinism convention -- the same bits on the same data;
+ * device X needs ldx >= d rounded up to 8, 16, 32, 64 or 128 (whole padded rows are read).  d > 128 (ldx >= d): A is formed once
+ * in the matrix' scratch, X staged as float64 panels, rr_gemm_tn_f64_kernel contracts them over the row slabs of rr_glm64_plan's
+ * rule (RR_GLM64_KSLABS forces the count) and the slabs are added in slab order: no floating-point atomics in either determinism
+ * mode.  The "rows first" / "step first" refusals of the _rff functions apply; every check is made before any launch. */
+#define RR_FEATMAT64_XT_MAX_DIM 4096
+int rr_featmat64_put_fastfood(rr_featmat64 *fm, rr_basis *fastfood, const void *dX, int x_dtype, int64_t ldx,
+                              const double *lenscale, int n_ls, int64_t col0);
+int rr_featmat64_put_fastfood_gm(rr_featmat64 *fm, rr_basis *fastfood, const void *dX, int x_dtype, int64_t ldx,
+                                 const double *mean, const double *lenscale, int n_ls, int64_t col0);
+int rr_featmat64_pass2_xt(rr_featmat64 *fm, const void *dX, int x_dtype, int64_t ldx, int d, int n, int64_t col0, double *dT);
+int rr_featmat64_glm_xt(rr_featmat64 *fm, const void *dX, int x_dtype, int64_t ldx, int d, int n, int64_t col0, double *dT);
 /* The rows of the current rr_featmat64_begin as they sit in HBM: out host float64 (rows, ld), ld = F rounded up to a multiple
  * of 128, padding columns included.  For tests and diagnostics. */
 int rr_featmat64_download(rr_featmat64 *fm, double *out);

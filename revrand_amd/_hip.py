@@ -150,6 +150,14 @@ SIGNATURES = {
                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "rr_featmat64_glm_centres": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                 ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "rr_featmat64_put_fastfood": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
+    "rr_featmat64_put_fastfood_gm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
+    "rr_featmat64_pass2_xt": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),
+    "rr_featmat64_glm_xt": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),
     "rr_featmat64_glm_edphi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "rr_featmat64_project": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "rr_rff_elbo_pass2_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
@@ -1702,6 +1710,29 @@ class FeatureMatrix64(object):
         """dg += sum(EdPhi o dPhi_i) per length scale of a centres child, after a GLM step, in float64."""
         _check(self.lib, self.lib.rr_featmat64_glm_centres(self.h, handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, col0, _ptr(dg)))
 
+    # -- FastFoodRBF / FastFoodGM children: the chain kernels' float64 instances, the handle-free contraction ----------------
+    def put_fastfood(self, ff_handle, dX, lenscale, col0):
+        """FastFoodRBF's chain features of the rows dX (float32 or float64) into columns [col0, col0 + 2 d2 k), in float64
+        whatever the handle's own arithmetic (rr_featmat64_put_fastfood)."""
+        ls, lsp, nls = _lenscale_arg(lenscale)
+        _check(self.lib, self.lib.rr_featmat64_put_fastfood(self.h, ff_handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, lsp, nls, col0))
+
+    def put_fastfood_gm(self, ff_handle, dX, mean, lenscale, col0):
+        """FastFoodGM's four blocks of the rows dX by the chain kernel into columns [col0, col0 + 4 d2 k), in float64."""
+        ls, lsp, nls = _lenscale_arg(lenscale)
+        mu = np.ascontiguousarray(mean, dtype=np.float64)
+        _check(self.lib, self.lib.rr_featmat64_put_fastfood_gm(self.h, ff_handle.h, dX.ptr, rr_dtype(dX.dtype), dX.ld,
+                                                               mu.ctypes.data_as(ctypes.c_void_p), lsp, nls, col0))
+
+    def pass2_xt(self, dX, d, n, col0, dT):
+        """dT (d, n) += X^T A for the trig block pair at [col0, col0 + 2n) after pass2_rows: pass2_rff without a random Fourier
+        handle, 1 <= d <= XT_MAX_DIM (rr_featmat64_pass2_xt)."""
+        _check(self.lib, self.lib.rr_featmat64_pass2_xt(self.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, int(d), int(n), col0, _ptr(dT)))
+
+    def glm_xt(self, dX, d, n, col0, dT):
+        """The same against EdPhi of the last GLM step (rr_featmat64_glm_xt)."""
+        _check(self.lib, self.lib.rr_featmat64_glm_xt(self.h, dX.ptr, rr_dtype(dX.dtype), dX.ld, int(d), int(n), col0, _ptr(dT)))
+
     def glm_edphi(self, rows, col0, ncols):
         E = np.empty((rows, ncols))
         _check(self.lib, self.lib.rr_featmat64_glm_edphi(self.h, col0, ncols, E.ctypes.data_as(ctypes.c_void_p)))
@@ -1716,6 +1747,18 @@ class FeatureMatrix64(object):
         _check(self.lib, self.lib.rr_featmat64_project(self.h, W.ctypes.data_as(ctypes.c_void_p), W.shape[1],
                                                        out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+
+XT_MAX_DIM = 4096          # RR_FEATMAT64_XT_MAX_DIM: the widest rows of FeatureMatrix64.pass2_xt / glm_xt
+
+
+def xt_padded_dim(d):
+    """The leading dimension pass2_xt / glm_xt need of their device X: d rounded up to 8, 16, 32, 64 or 128 for the register
+    kernel (d <= 128), d itself above (the GEMM route stages its own panels)."""
+    for p in (8, 16, 32, 64, 128):
+        if d <= p:
+            return p
+    return int(d)
 
 
 def glm64_plan(rows, F, KL, num_cu):

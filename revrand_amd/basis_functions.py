@@ -588,6 +588,69 @@ class _ResidentFastFoodGM(_ResidentRFF):
         self.dTm.free()
 
 
+def _chain_state64(child, basis, X):
+    """What the float64 FastFood children keep: the chain handle, V = _makeVX(I_d) on the host (from the chain itself,
+    rr_fastfood_vx on the identity -- no dense random Fourier handle is built), X resident as float64 with the leading
+    dimension both the chain kernel (>= d) and the contraction (_hip.xt_padded_dim; even, so that rows stay 16-byte
+    aligned) accept, and a zeroed T."""
+    child.basis = basis
+    child.ff, lazy = basis._handles()
+    child.h = child.ff   # (`reset`, `dhyp` and `release` reach the device through `h.dev`)
+    if basis.dtype == "f64":
+        if lazy.V is None:
+            lazy.V = child.ff.vx(np.eye(basis.d), 1.0)
+        V = lazy.V
+    else:
+        # an f32 basis in a float64 state: its features come from the chain's float64 instance, so V must be the float64
+        # chain's too (the handle's own rr_fastfood_vx runs in float32) -- from a float64 twin of the handle, once
+        V = lazy.__dict__.get("V64")
+        if V is None:
+            twin = _hip.FastFoodHandle(basis.d, basis.d2, basis.k, basis.B, basis.G, basis.PI, basis.S, compute="f64", wide=True)
+            V = lazy.V64 = twin.vx(np.eye(basis.d), 1.0)
+    child.W = np.asarray(V, dtype=np.float64)
+    ld = _hip.xt_padded_dim(basis.d)
+    child.dX = child.ff.dev.upload_matrix(np.ascontiguousarray(X, dtype=np.float64), ld_dev=ld + (ld & 1))
+    child.dT = child.ff.dev.zeros(child.W.size * 8)
+
+
+class _ResidentFastFood64(_ResidentFastFood):
+    """FastFoodRBF child of a FLOAT64 state (FeatureMatrix64; resident_bases="all"): the chain kernels' float64 instances
+    write Phi (rr_featmat64_put_fastfood, whatever the basis' own dtype), T = X^T A by the handle-free contraction
+    (rr_featmat64_pass2_xt / _glm_xt: the register kernel up to 128 input columns, the float64 GEMM up to 4096) and `dhyp` is
+    the f32 class' formula with V on the host.  `put` / `put_batch` / `gather` / `dhyp` are the f32 classes' own."""
+
+    def __init__(self, basis, X):
+        _chain_state64(self, basis, X)
+
+    def grad(self, fm, r0, rows, col0):
+        fm.pass2_xt(_hip.DeviceView(self.dX, r0, rows), self.basis.d, self.ff.n, col0, self.dT)
+
+    def glm_grad(self, fm, M, col0):
+        """The same contraction against EdPhi of a GLM minibatch step (glm.py:274-275)."""
+        fm.glm_xt(self.batch(M), self.basis.d, self.ff.n, col0, self.dT)
+
+
+class _ResidentFastFoodGM64(_ResidentFastFoodGM):
+    """FastFoodGM child of a float64 state: the four blocks by the chain's mixture mode in float64
+    (rr_featmat64_put_fastfood_gm), T+ / T- by the handle-free contraction at col0 and col0 + 2n."""
+
+    def __init__(self, basis, X):
+        _chain_state64(self, basis, X)
+        self.dense = False
+        self.dTm = self.ff.dev.zeros(self.W.size * 8)
+        self.n = self.ff.n
+
+    def grad(self, fm, r0, rows, col0):
+        view = _hip.DeviceView(self.dX, r0, rows)
+        fm.pass2_xt(view, self.basis.d, self.n, col0, self.dT)
+        fm.pass2_xt(view, self.basis.d, self.n, col0 + 2 * self.n, self.dTm)
+
+    def glm_grad(self, fm, M, col0):
+        view = self.batch(M)
+        fm.glm_xt(view, self.basis.d, self.n, col0, self.dT)
+        fm.glm_xt(view, self.basis.d, self.n, col0 + 2 * self.n, self.dTm)
+
+
 class _ResidentCentres(object):
     """RadialBasis / SigmoidalBasis child: X resident as float32 (N, d); features by rr_featmat_put_centres, the length
     scales' gradient contracted on the device against the second pass' (or the GLM step's) scratch into `dg` -- one float64
@@ -789,10 +852,10 @@ class MinibatchFeatures(object):
         self._drop_children()
         kids = []
         for b in self.bases:
-            if resident_bases == "all" and getattr(b, "_child_options", False):
-                c = b._resident_child(X, wide=True)
-            elif dense_gm and getattr(b, "_dense_child_option", False):
+            if dense_gm and getattr(b, "_dense_child_option", False):   # (first: a FastFoodGM takes both sets of options)
                 c = b._resident_child(X, dense_gm=True)
+            elif resident_bases == "all" and getattr(b, "_child_options", False):
+                c = b._resident_child(X, wide=True)
             else:
                 c = b._resident_child(X)
             if c is None:
@@ -928,7 +991,7 @@ class MinibatchFeatures(object):
                 child.reset()
                 child.glm_grad(self.fm, self.M, col0)
                 g = child.dhyp(1.0)
-            elif isinstance(child, _ResidentCentres):
+            elif isinstance(child, (_ResidentCentres, _ResidentFastFood64)):
                 child.reset()
                 child.glm_grad(self.fm, self.M, col0)
                 g = [child.dhyp(1.0)]   # -(EdPhi o dPhi_i).sum(), contracted on the device
@@ -999,9 +1062,10 @@ class MinibatchFeatures64(MinibatchFeatures):
     the step in float64, ``y`` and the per-row likelihood argument staged as float64 (counts above 2^24 stay exact), the draws
     taken as host float64.  The children are the float64 states' (``_resident_child(X, dtype="f64", ...)``, as BasisCat's float64
     fit state asks): random Fourier children of Xdim <= 128 (their rows resident as float64 whatever the basis' own dtype) and
-    LinearBasis on the device; under resident_bases="all" RadialBasis / SigmoidalBasis / PolynomialBasis too; every other basis
-    (FastFoodRBF, FastFoodGM, wide inputs) through its own ``transform`` and ``put_host``, its gradient from the downloaded EdPhi
-    block and ``basis.grad`` on the host.  ``make_resident`` works when every child can gather float64 rows; otherwise the rows
+    LinearBasis on the device; under resident_bases="all" RadialBasis / SigmoidalBasis / PolynomialBasis and FastFoodRBF /
+    FastFoodGM (the chain in float64, inputs up to 4096 columns) too; every other basis (the FastFood bases by default, wide
+    random Fourier inputs) through its own ``transform`` and ``put_host``, its gradient from the downloaded EdPhi block and
+    ``basis.grad`` on the host.  ``make_resident`` works when every child can gather float64 rows; otherwise the rows
     come from the host per step.  No device sampler, no device-resident draws, no ``predictive``."""
 
     _target_dtype = np.float64
@@ -1507,10 +1571,19 @@ class FastFoodRBF(_LengthScaleBasis):
         lazy = self._handles()[1]
         return lazy.get(), lazy.V
 
+    _child_options = True  # `_resident_child` takes the options of resident_bases="all": f64_children (a float64 state's
+    #                        opt-in) and wide (the centre bases' alone, ignored here)
+
     @slice_transform
-    def _resident_child(self, X, dtype=None):
-        """This basis' share of a device-resident fit (f32 states): features by the chain kernel."""
-        if self.dtype != "f32" or dtype == "f64" or X.shape[1] != self.d or type(self)._resident_via_chain is False:
+    def _resident_child(self, X, dtype=None, f64_children=False, wide=False):
+        """This basis' share of a device-resident fit: features by the chain kernel.  f32 states take f32 bases; a float64
+        state takes this basis -- whatever its own dtype: the float64 matrix runs the chain in float64 -- only when its maker
+        opted in (f64_children: resident_bases="all")."""
+        if X.shape[1] != self.d or type(self)._resident_via_chain is False:
+            return None
+        if dtype == "f64":
+            return _ResidentFastFood64(self, X) if f64_children else None
+        if self.dtype != "f32":
             return None
         return _ResidentFastFood(self, X)
 
@@ -1518,13 +1591,18 @@ class FastFoodRBF(_LengthScaleBasis):
     _wide_chain = True  # block sizes 512 .. 4096 (256 < Xdim <= 4096) by rr_fastfood_create_wide; FastFoodGM: up to 256 only
 
     @slice_transform
-    def device_fit_state(self, X, y):
+    def device_fit_state(self, X, y, resident_bases="fourier"):
         """(X, y) resident for a whole fit.  f32: the statistics pass runs the CHAIN (rr_fastfood16_kernel, or
         rr_fastfood64_kernel at Xdim > 256 -> feature matrix
         -> MFMA SYRK) and the second pass contracts X^T A against the same features -- a one-child CatFitState.  f64 (or
-        RR_FASTFOOD_FIT=dense, A/B runs): the dense equivalent W through the random Fourier kernels."""
+        RR_FASTFOOD_FIT=dense, A/B runs): the dense equivalent W through the random Fourier kernels.  resident_bases="all":
+        a dtype="f64" basis gets a float64 one-child CatFitState on the chain instead (inputs up to 4096 columns)."""
         if X.shape[1] != self.d:
             return None
+        if resident_bases == "all" and self.dtype == "f64" and self._resident_via_chain:
+            import types
+            return CatFitState(types.SimpleNamespace(get_dim=self.get_dim, bases=[self]), [_ResidentFastFood64(self, X)], X, y,
+                               dtype="f64")
         if self.dtype == "f32" and self._resident_via_chain and _hip.os.environ.get("RR_FASTFOOD_FIT", "chain") != "dense":
             import types
             return CatFitState(types.SimpleNamespace(get_dim=self.get_dim, bases=[self]), [_ResidentFastFood(self, X)], X, y)
@@ -1624,9 +1702,13 @@ class FastFoodGM(FastFoodRBF):
     _dense_child_option = True  # `_resident_child` takes dense_gm (the estimator's fused_bases="all+gm", through make_resident)
 
     @slice_transform
-    def _resident_child(self, X, dtype=None, dense_gm=False):
-        if dtype == "f64" or X.shape[1] != self.d:
+    def _resident_child(self, X, dtype=None, dense_gm=False, f64_children=False, wide=False):
+        if X.shape[1] != self.d:
             return None
+        if dtype == "f64":
+            # a float64 state: only for a maker that opted in (resident_bases="all"), and where the chain's mixture mode serves
+            # the block size (16 <= d2 <= 256, or a wide_chain=True handle) -- in float64 whatever this basis' own dtype
+            return _ResidentFastFoodGM64(self, X) if f64_children and self._handles()[0].gm_chain_ok else None
         if not self._chain_fit_ok():
             # block sizes BELOW the chain's mixture mode (d2 < 16, i.e. Xdim <= 8): only for a maker that opted in, and then on
             # the dense handle alone.  (Block sizes above it -- Xdim > 256 without wide_chain=True -- have no FastFoodGM handle at all: no child.)
@@ -1636,11 +1718,15 @@ class FastFoodGM(FastFoodRBF):
         return _ResidentFastFoodGM(self, X)
 
     @slice_transform
-    def device_fit_state(self, X, y):
-        """(X, y) resident for a whole fit: a one-child CatFitState whose child writes the four blocks with the chain kernel."""
+    def device_fit_state(self, X, y, resident_bases="fourier"):
+        """(X, y) resident for a whole fit: a one-child CatFitState whose child writes the four blocks with the chain kernel.
+        resident_bases="all": a dtype="f64" basis gets a float64 one instead of declining."""
+        import types
+        if resident_bases == "all" and self.dtype == "f64" and X.shape[1] == self.d and self._handles()[0].gm_chain_ok:
+            return CatFitState(types.SimpleNamespace(get_dim=self.get_dim, bases=[self]), [_ResidentFastFoodGM64(self, X)], X, y,
+                               dtype="f64")
         if not self._chain_fit_ok() or X.shape[1] != self.d:
             return None
-        import types
         return CatFitState(types.SimpleNamespace(get_dim=self.get_dim, bases=[self]), [_ResidentFastFoodGM(self, X)], X, y)
 
     @slice_transform

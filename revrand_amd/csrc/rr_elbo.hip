@@ -4235,10 +4235,11 @@ static void fm64_free_scratch(rr_featmat64 *fm) {
     fm->glm = nullptr;
     fm->have_edphi = false;
     fm->have_post = false;
-    void *q[] = {fm->Pt, fm->U, fm->Cp, fm->Craw, fm->m, fm->dot, fm->err, fm->sq, fm->vf};
+    void *q[] = {fm->Pt, fm->U, fm->Cp, fm->Craw, fm->m, fm->dot, fm->err, fm->sq, fm->vf, fm->xt};
     for (void *x : q)
         if (x) (void)hipFree(x);
-    fm->Pt = fm->U = fm->Cp = fm->Craw = fm->m = fm->dot = fm->err = fm->sq = fm->vf = nullptr;
+    fm->Pt = fm->U = fm->Cp = fm->Craw = fm->m = fm->dot = fm->err = fm->sq = fm->vf = fm->xt = nullptr;
+    fm->xt_elems = 0;
 }
 
 int rr_fm64_scratch(rr_featmat64 *fm) {
@@ -4270,6 +4271,44 @@ static int fm64_products(rr_featmat64 *fm) {
                        fm->rows, Fp, fm->Pt, fm->max_rows);
     RR_CHECK_HIP(hipGetLastError());
     return rr_launch_gemm_tn_f64(c, fm->Pt, fm->max_rows, fm->Cp, Fp, fm->U, Fp, ((int64_t)fm->F + 15) / 16 * 16, rp, Fp, 0, 0);
+}
+
+// rr_grad_t64_kernel over the rows in the matrix for the trig block pair at [col0, col0 + 2n): dT (d, n) += X^T A after
+// pass2_rows (d <= dpad <= 128, ldx >= dpad); block partials by atomics, or -- deterministic -- added in block order
+static int fm64_pass2_t(rr_featmat64 *fm, const void *dX, int x_dtype, int64_t ldx, int d, int dpad, int n, int64_t col0, double *dT) {
+    rr_ctx *c = fm->ctx;
+    RR_CHECK_HIP(hipSetDevice(c->device));
+    const int64_t mrows = fm->rows;
+    const int fblocks = (n + 255) / 256;
+    int64_t rpb = (mrows * fblocks + (int64_t)c->num_cu * 8 - 1) / ((int64_t)c->num_cu * 8);
+    if (rpb < 64) rpb = 64;
+    if ((mrows + rpb - 1) / rpb > 65535) rpb = (mrows + 65534) / 65535;
+    const dim3 grid(fblocks, (unsigned)((mrows + rpb - 1) / rpb));
+    const int64_t tcount = (int64_t)d * n, tdet = c->deterministic ? tcount : 0;
+    double *Tdst = dT;
+    if (tdet) {
+        void *part = nullptr;
+        int rc = rr_det_scratch(c, (size_t)grid.y * (size_t)tcount * 8, &part);
+        if (rc != RR_OK) return rc;
+        Tdst = (double *)part;
+    }
+#define RR_FGT(DM, TX)                                                                                                    \
+    hipLaunchKernelGGL((rr_grad_t64_kernel<DM, TX>), grid, dim3(256), 0, c->stream, (const TX *)dX, mrows, ldx, fm->P + col0, \
+                       fm->U + col0, fm->ld, fm->err, fm->m + col0, n, d, Tdst, (int)rpb, tdet)
+#define RR_FGTD(DM)                          \
+    if (x_dtype == RR_F32) RR_FGT(DM, float); \
+    else RR_FGT(DM, double)
+    switch (dpad) {
+        case 8: RR_FGTD(8); break;
+        case 16: RR_FGTD(16); break;
+        case 32: RR_FGTD(32); break;
+        case 64: RR_FGTD(64); break;
+        default: RR_FGTD(128); break;
+    }
+#undef RR_FGTD
+#undef RR_FGT
+    RR_CHECK_HIP(hipGetLastError());
+    return tdet ? rr_det_reduce(c, Tdst, grid.y, tcount, tcount, dT) : RR_OK;
 }
 
 extern "C" {
@@ -4514,40 +4553,25 @@ int rr_featmat64_pass2_rff(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_
     RR_REQUIRE(ldx >= b->dpad && !b->large, "rr_featmat64_pass2_rff: device X needs ldx >= rr_rff_padded_dim() = %d, Xdim <= 128", b->dpad);
     if (fm->rows == 0) return RR_OK;
     RR_REQUIRE(dX != nullptr, "rr_featmat64_pass2_rff: null X");
-    rr_ctx *c = fm->ctx;
-    RR_CHECK_HIP(hipSetDevice(c->device));
-    const int n = b->n;
-    const int64_t mrows = fm->rows;
-    const int fblocks = (n + 255) / 256;
-    int64_t rpb = (mrows * fblocks + (int64_t)c->num_cu * 8 - 1) / ((int64_t)c->num_cu * 8);
-    if (rpb < 64) rpb = 64;
-    if ((mrows + rpb - 1) / rpb > 65535) rpb = (mrows + 65534) / 65535;
-    const dim3 grid(fblocks, (unsigned)((mrows + rpb - 1) / rpb));
-    const int64_t tcount = (int64_t)b->d * n, tdet = c->deterministic ? tcount : 0;
-    double *Tdst = dT;
-    if (tdet) {
-        void *part = nullptr;
-        int rc = rr_det_scratch(c, (size_t)grid.y * (size_t)tcount * 8, &part);
-        if (rc != RR_OK) return rc;
-        Tdst = (double *)part;
-    }
-#define RR_FGT(DM, TX)                                                                                                    \
-    hipLaunchKernelGGL((rr_grad_t64_kernel<DM, TX>), grid, dim3(256), 0, c->stream, (const TX *)dX, mrows, ldx, fm->P + col0, \
-                       fm->U + col0, fm->ld, fm->err, fm->m + col0, n, b->d, Tdst, (int)rpb, tdet)
-#define RR_FGTD(DM)                          \
-    if (x_dtype == RR_F32) RR_FGT(DM, float); \
-    else RR_FGT(DM, double)
-    switch (b->dpad) {
-        case 8: RR_FGTD(8); break;
-        case 16: RR_FGTD(16); break;
-        case 32: RR_FGTD(32); break;
-        case 64: RR_FGTD(64); break;
-        default: RR_FGTD(128); break;
-    }
-#undef RR_FGTD
-#undef RR_FGT
-    RR_CHECK_HIP(hipGetLastError());
-    return tdet ? rr_det_reduce(c, Tdst, grid.y, tcount, tcount, dT) : RR_OK;
+    return fm64_pass2_t(fm, dX, x_dtype, ldx, b->d, b->dpad, b->n, col0, dT);
+}
+
+// The same contraction for any trig block pair [cos | sin] at [col0, col0 + 2n) and rows of 1 <= d <= 4096 columns, without a
+// random Fourier handle (the FastFood children of the float64 matrix: their blocks come from the chain kernels).  d <= 128:
+// rr_grad_t64_kernel exactly as above (ldx >= d rounded up to 8, 16, 32, 64 or 128: the kernel reads whole padded rows).
+// d > 128: A is formed once and contracted with X on the float64 GEMM (rr_fm64_xt_wide, rr_glm64.hip), ldx >= d.
+int rr_featmat64_pass2_xt(rr_featmat64 *fm, const void *dX, int x_dtype, int64_t ldx, int d, int n, int64_t col0, double *dT) {
+    RR_REQUIRE(fm != nullptr && fm->Pt != nullptr && fm->have_rows, "rr_featmat64_pass2_xt: call rr_featmat64_pass2_rows first");
+    RR_REQUIRE(dT != nullptr && n >= 1, "rr_featmat64_pass2_xt: bad argument");
+    RR_REQUIRE(d >= 1 && d <= RR_FM64_XT_MAX_DIM, "rr_featmat64_pass2_xt: needs 1 <= Xdim <= %d, got %d", RR_FM64_XT_MAX_DIM, d);
+    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_featmat64_pass2_xt: bad dtype");
+    RR_REQUIRE(col0 >= 0 && col0 + 2 * (int64_t)n <= fm->F, "rr_featmat64_pass2_xt: columns out of range");
+    const int dpad = rr_fm64_xt_dpad(d);
+    RR_REQUIRE(ldx >= dpad, "rr_featmat64_pass2_xt: device X needs ldx >= %d for Xdim = %d", dpad, d);
+    if (fm->rows == 0) return RR_OK;
+    RR_REQUIRE(dX != nullptr, "rr_featmat64_pass2_xt: null X");
+    if (d > 128) return rr_fm64_xt_wide(fm, false, dX, x_dtype, ldx, d, n, col0, dT);
+    return fm64_pass2_t(fm, dX, x_dtype, ldx, d, dpad, n, col0, dT);
 }
 
 int rr_featmat64_pass2_end(rr_featmat64 *fm, double *sqErr) {

@@ -1116,8 +1116,10 @@ static int ff_launch(rr_basis *b, const void *dX, int64_t N, int64_t ldx, void *
 
 template <bool PHI, bool GM = false>
 static int ff_dispatch(rr_basis *b, const void *dX, int x_dtype, int64_t N, int64_t ldx, void *dOut, int out_dtype,
-                       int64_t ldo) {
-    const int key = x_dtype * 4 + b->compute * 2 + out_dtype;
+                       int64_t ldo, bool force_f64 = false) {
+    // force_f64: the float64 instance whatever the handle's own arithmetic (the float64 feature matrix; every handle carries
+    // both table sets)
+    const int key = x_dtype * 4 + (force_f64 ? RR_F64 : b->compute) * 2 + out_dtype;
     switch (key) {
         case 0: return ff_launch<PHI, float, float, float, GM>(b, dX, N, ldx, dOut, ldo);
         case 1: return ff_launch<PHI, float, float, double, GM>(b, dX, N, ldx, dOut, ldo);
@@ -1379,6 +1381,46 @@ int rr_featmat_put_fastfood_gm(rr_featmat *fm, rr_basis *b, const void *dX, int 
     rc = rr_fm_claim(fm, col0, 4 * (int64_t)b->n, "rr_featmat_put_fastfood_gm");
     if (rc != RR_OK) return rc;
     return ff_dispatch<true, true>(b, dX, x_dtype, fm->rows, ldx, fm->P + col0, RR_F32, fm->ld);
+}
+
+// The same two puts into the FLOAT64 feature matrix (rr_featmat64, rr_elbo.hip): the chain's float64 instance whatever the
+// handle's compute (its float64 tables), double output at the matrix' leading dimension, any col0 (an odd one takes the
+// kernels' scalar-store instances); columns outside the block and the matrix' padding are left alone.
+int rr_featmat64_put_fastfood(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *lenscale,
+                              int n_ls, int64_t col0) {
+    RR_REQUIRE(fm != nullptr && b != nullptr && b->kind == RR_KIND_FASTFOOD, "rr_featmat64_put_fastfood: not a FastFood basis");
+    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_featmat64_put_fastfood: bad dtype");
+    RR_REQUIRE(b->ctx == fm->ctx, "rr_featmat64_put_fastfood: basis and feature matrix live on different device contexts");
+    RR_REQUIRE(col0 >= 0 && col0 + 2 * (int64_t)b->n <= fm->F, "rr_featmat64_put_fastfood: columns out of range");
+    RR_REQUIRE(ldx >= b->d, "rr_featmat64_put_fastfood: bad shape");
+    RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
+    int rc = ff_prepare_lenscale(b, lenscale, n_ls);
+    if (rc != RR_OK || fm->rows == 0) return rc;
+    RR_REQUIRE(dX != nullptr, "rr_featmat64_put_fastfood: null X");
+    rc = rr_fm64_claim(fm, col0, 2 * (int64_t)b->n, "rr_featmat64_put_fastfood");
+    if (rc != RR_OK) return rc;
+    return ff_dispatch<true>(b, dX, x_dtype, fm->rows, ldx, fm->P + col0, RR_F64, fm->ld, true);
+}
+
+int rr_featmat64_put_fastfood_gm(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_dtype, int64_t ldx, const double *mean,
+                                 const double *lenscale, int n_ls, int64_t col0) {
+    RR_REQUIRE(fm != nullptr && b != nullptr && b->kind == RR_KIND_FASTFOOD, "rr_featmat64_put_fastfood_gm: not a FastFood basis");
+    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_featmat64_put_fastfood_gm: bad dtype");
+    RR_REQUIRE(b->ctx == fm->ctx, "rr_featmat64_put_fastfood_gm: basis and feature matrix live on different device contexts");
+    RR_REQUIRE(col0 >= 0 && col0 + 4 * (int64_t)b->n <= fm->F, "rr_featmat64_put_fastfood_gm: columns out of range");
+    RR_REQUIRE(ldx >= b->d, "rr_featmat64_put_fastfood_gm: bad shape");
+    if ((b->ff_d2 < 16 || b->ff_d2 > 256) && !b->ff_wide_gm) {  // (before the columns are claimed: ff_launch would refuse after)
+        rr_set_error("fastfood: the mixture-component chain kernel serves 16 <= d2 <= 256 (d2 = %d: use the dense route)", b->ff_d2);
+        return RR_ERR_UNSUPPORTED;
+    }
+    RR_CHECK_HIP(hipSetDevice(fm->ctx->device));
+    int rc = ff_prepare_lenscale(b, lenscale, n_ls);
+    if (rc == RR_OK) rc = ff_prepare_mean(b, mean);
+    if (rc != RR_OK || fm->rows == 0) return rc;
+    RR_REQUIRE(dX != nullptr, "rr_featmat64_put_fastfood_gm: null X");
+    rc = rr_fm64_claim(fm, col0, 4 * (int64_t)b->n, "rr_featmat64_put_fastfood_gm");
+    if (rc != RR_OK) return rc;
+    return ff_dispatch<true, true>(b, dX, x_dtype, fm->rows, ldx, fm->P + col0, RR_F64, fm->ld, true);
 }
 
 int rr_fastfood_vx(rr_basis *b, const void *X, int x_dtype, int64_t N, int64_t ldx, const double *lenscale, int n_ls,

@@ -24,6 +24,7 @@
 // its softplus-link Poisson keeps the reference's clamp where this one is division-free).  tests/glm_f64_cases.py holds these
 // to (16 + 4 |f|) 2^-53 S per element over -200 <= f <= 200.
 // =============================================================================================
+#include <algorithm>
 #include <cstdlib>
 
 #include "rr_internal.h"
@@ -254,6 +255,149 @@ rr_glm_grad_t64_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, const d
     }
 }
 
+// ---- the wide contraction T = X^T A (rr_featmat64_pass2_xt / rr_featmat64_glm_xt, 128 < Xdim <= 4096) ----------------------------
+// A one-frequency-per-thread VALU kernel holds Xdim accumulators in registers; above 128 columns the 2 rows d n flops go to the
+// float64 matrix cores instead: A (rows_pad, npad) is formed once in the matrix' Pt scratch (free once U holds Phi C or EdPhi),
+// X is staged as float64 (rows_pad, wp) panels of at most wp columns, rr_gemm_tn_f64_kernel contracts them over its row slabs
+// (glm64_plan's rule: tiles = (wp / 128)(npad / 128)) and the slabs' tiles are added into T in slab order.  npad, wp: multiples
+// of 128; every padded element of both operands is written as zero.  No atomics: the same bits every run.
+
+// A[r][f] for the trig block pair (P, U point at the pair's first column; 2 n <= ldp - col0).  GLM: E_s P_c - E_c P_s against
+// the stored EdPhi (U); else err (P_c m_s - P_s m_c) - (P_c U_s - P_s U_c), the operand of rr_grad_t64_kernel.  A wave writes
+// 64 double2 = one 1 KiB run of a row; 4 rows per block pass, blocks stride over the rows.
+template <bool GLM>
+__global__ void __launch_bounds__(256)
+rr_fm64_form_a_kernel(const double *__restrict__ P, const double *__restrict__ U, int64_t ldp, int64_t col0,
+                      const double *__restrict__ err, const double *__restrict__ mvec, int64_t rows, int64_t rows_pad, int n,
+                      int64_t npad, double *__restrict__ A) {
+    const int f = 2 * (blockIdx.x * 64 + (threadIdx.x & 63));
+    RR_DEV_ASSERT(f + 2 <= npad && n <= npad && col0 + 2 * (int64_t)n <= ldp && rows <= rows_pad);
+    const bool v0 = f < n, v1 = f + 1 < n;
+    const int f0 = v0 ? f : 0, f1 = v1 ? f + 1 : 0;
+    double mc0 = 0.0, mc1 = 0.0, ms0 = 0.0, ms1 = 0.0;
+    if (!GLM) {
+        mc0 = mvec[f0];
+        mc1 = mvec[f1];
+        ms0 = mvec[n + f0];
+        ms1 = mvec[n + f1];
+    }
+    for (int64_t r = (int64_t)blockIdx.y * 4 + (threadIdx.x >> 6); r < rows_pad; r += (int64_t)gridDim.y * 4) {
+        double2 a;
+        a.x = 0.0;
+        a.y = 0.0;
+        if (r < rows) {
+            const double *p = P + r * ldp, *u = U + r * ldp;
+            const double pc0 = p[f0], pc1 = p[f1], ps0 = p[n + f0], ps1 = p[n + f1];
+            const double uc0 = u[f0], uc1 = u[f1], us0 = u[n + f0], us1 = u[n + f1];
+            if (GLM) {
+                a.x = us0 * pc0 - uc0 * ps0;
+                a.y = us1 * pc1 - uc1 * ps1;
+            } else {
+                const double e = err[r];
+                a.x = e * (pc0 * ms0 - ps0 * mc0) - (pc0 * us0 - ps0 * uc0);
+                a.y = e * (pc1 * ms1 - ps1 * mc1) - (pc1 * us1 - ps1 * uc1);
+            }
+            if (!v0) a.x = 0.0;
+            if (!v1) a.y = 0.0;
+        }
+        *reinterpret_cast<double2 *>(A + r * npad + f) = a;
+    }
+}
+
+// Xs (rows_pad, wp) = the columns [i0, i0 + w) of X (rows, ldx) as float64, zero beyond w and beyond `rows`
+template <typename TX>
+__global__ void __launch_bounds__(256)
+rr_fm64_stage_x_kernel(const TX *__restrict__ X, int64_t rows, int64_t rows_pad, int64_t ldx, int i0, int w, int64_t wp,
+                       double *__restrict__ Xs) {
+    const int c = 2 * (blockIdx.x * 64 + (threadIdx.x & 63));
+    RR_DEV_ASSERT(c + 2 <= wp && w <= wp && i0 + w <= ldx && rows <= rows_pad);
+    for (int64_t r = (int64_t)blockIdx.y * 4 + (threadIdx.x >> 6); r < rows_pad; r += (int64_t)gridDim.y * 4) {
+        double2 v;
+        v.x = 0.0;
+        v.y = 0.0;
+        if (r < rows) {
+            const TX *x = X + r * ldx + i0;
+            if (c < w) v.x = (double)x[c];
+            if (c + 1 < w) v.y = (double)x[c + 1];
+        }
+        *reinterpret_cast<double2 *>(Xs + r * wp + c) = v;
+    }
+}
+
+// T[(i0 + i) n + f] += sum_s part[s stride + i npad + f] in slab order, i < w, f < n
+__global__ void __launch_bounds__(256)
+rr_fm64_xt_sum_kernel(const double *__restrict__ part, int nslabs, int64_t stride, int64_t npad, int n, int i0, int w,
+                      double *__restrict__ T) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    const int i = blockIdx.y;
+    if (f >= n) return;
+    RR_DEV_ASSERT(i < w && n <= npad && (int64_t)w * npad <= stride);
+    double a = part[(int64_t)i * npad + f];
+    for (int s = 1; s < nslabs; ++s) a += part[(int64_t)s * stride + (int64_t)i * npad + f];
+    T[(int64_t)(i0 + i) * n + f] += a;
+}
+
+int rr_fm64_xt_wide(rr_featmat64 *fm, bool glm, const void *dX, int x_dtype, int64_t ldx, int d, int n, int64_t col0, double *dT) {
+    rr_ctx *c = fm->ctx;
+    RR_CHECK_HIP(hipSetDevice(c->device));
+    const int64_t rp = fm->rows_pad, npad = ((int64_t)n + 127) / 128 * 128, dp = ((int64_t)d + 127) / 128 * 128;
+    RR_REQUIRE(fm->Pt != nullptr && npad <= fm->ld && rp <= fm->max_rows, "float64 feature matrix: no room for the contraction's operand");
+    // X panels of at most 2^27 staged elements (1 GiB)
+    int64_t wp = ((int64_t)1 << 27) / rp / 128 * 128;
+    if (wp < 128) wp = 128;
+    if (wp > dp) wp = dp;
+    const char *fs = getenv("RR_GLM64_KSLABS");  // measurement switch: force the slab count (as the step's Ed product)
+    const int force = fs ? atoi(fs) : 0;
+    size_t need = 0;
+    for (int64_t i0 = 0; i0 < d; i0 += wp) {
+        const int64_t w = std::min<int64_t>(wp, d - i0), w128 = (w + 127) / 128 * 128;
+        int64_t plan[4];
+        glm64_plan(fm->rows, n, w128, c->num_cu, force, plan);
+        need = std::max(need, (size_t)(rp * w128 + plan[0] * w128 * npad));
+    }
+    if (fm->xt_elems < need) {
+        RR_CHECK_HIP(hipStreamSynchronize(c->stream));
+        if (fm->xt) (void)hipFree(fm->xt);
+        fm->xt = nullptr;
+        fm->xt_elems = 0;
+        if (hipMalloc((void **)&fm->xt, need * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            rr_set_error("float64 feature matrix: device allocation of the wide contraction's scratch (%zu bytes) failed", need * 8);
+            return RR_ERR_OOM;
+        }
+        fm->xt_elems = need;
+    }
+    double *A = fm->Pt;
+    const unsigned gy = (unsigned)std::min<int64_t>((rp + 3) / 4, 65535);
+    if (glm)
+        hipLaunchKernelGGL(rr_fm64_form_a_kernel<true>, dim3((unsigned)(npad / 128), gy), dim3(256), 0, c->stream, fm->P + col0,
+                           fm->U + col0, fm->ld, col0, (const double *)nullptr, (const double *)nullptr, fm->rows, rp, n, npad, A);
+    else
+        hipLaunchKernelGGL(rr_fm64_form_a_kernel<false>, dim3((unsigned)(npad / 128), gy), dim3(256), 0, c->stream, fm->P + col0,
+                           fm->U + col0, fm->ld, col0, fm->err, fm->m + col0, fm->rows, rp, n, npad, A);
+    RR_CHECK_HIP(hipGetLastError());
+    for (int64_t i0 = 0; i0 < d; i0 += wp) {
+        const int64_t w = std::min<int64_t>(wp, d - i0), w128 = (w + 127) / 128 * 128;
+        double *Xs = fm->xt, *part = fm->xt + rp * w128;
+        if (x_dtype == RR_F32)
+            hipLaunchKernelGGL(rr_fm64_stage_x_kernel<float>, dim3((unsigned)(w128 / 128), gy), dim3(256), 0, c->stream, (const float *)dX,
+                               fm->rows, rp, ldx, (int)i0, (int)w, w128, Xs);
+        else
+            hipLaunchKernelGGL(rr_fm64_stage_x_kernel<double>, dim3((unsigned)(w128 / 128), gy), dim3(256), 0, c->stream, (const double *)dX,
+                               fm->rows, rp, ldx, (int)i0, (int)w, w128, Xs);
+        RR_CHECK_HIP(hipGetLastError());
+        int64_t plan[4];
+        glm64_plan(fm->rows, n, w128, c->num_cu, force, plan);
+        const int64_t stride = w128 * npad;
+        int rc = rr_launch_gemm_tn_f64_slabs(c, Xs, w128, A, npad, part, npad, rp, w128, npad, (int)plan[0], plan[1], stride);
+        if (rc != RR_OK) return rc;
+        hipLaunchKernelGGL(rr_fm64_xt_sum_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)w), dim3(256), 0, c->stream, part,
+                           (int)plan[0], stride, npad, n, (int)i0, (int)w, dT);
+        RR_CHECK_HIP(hipGetLastError());
+    }
+    return RR_OK;
+}
+
 // ---- scratch: next to the matrix' second-pass scratch (rr_featmat64::glm), allocated by the first step, grown when K L grows ----
 struct Glm64Scratch {
     double *WSs = nullptr, *WSt = nullptr, *FS = nullptr, *DFSt = nullptr, *Ed = nullptr, *Eraw = nullptr, *part = nullptr;
@@ -398,6 +542,44 @@ static int glm64_weights(rr_featmat64 *fm, Glm64Scratch &s, const double *src, b
     return RR_OK;
 }
 
+// rr_glm_grad_t64_kernel over the rows of the last step for the trig block pair at [col0, col0 + 2n): dT (d, n) += X^T A against
+// EdPhi (d <= dpad <= 128, ldx >= dpad); block partials by atomics, or -- deterministic -- added in block order
+static int glm64_grad_t(rr_featmat64 *fm, const void *dX, int x_dtype, int64_t ldx, int d, int dpad, int n, int64_t col0, double *dT) {
+    rr_ctx *c = fm->ctx;
+    RR_CHECK_HIP(hipSetDevice(c->device));
+    const int64_t N = fm->rows;
+    const int fblocks = (n + 255) / 256;
+    int64_t rpb = (N * fblocks + (int64_t)c->num_cu * 8 - 1) / ((int64_t)c->num_cu * 8);
+    if (rpb < 64) rpb = 64;
+    if ((N + rpb - 1) / rpb > 65535) rpb = (N + 65534) / 65535;
+    const dim3 grid(fblocks, (unsigned)((N + rpb - 1) / rpb));
+    const int64_t tcount = (int64_t)d * n, tdet = c->deterministic ? tcount : 0;
+    double *Tdst = dT;
+    if (tdet) {
+        void *part = nullptr;
+        int rc = rr_det_scratch(c, (size_t)grid.y * (size_t)tcount * 8, &part);
+        if (rc != RR_OK) return rc;
+        Tdst = (double *)part;
+    }
+#define RR_GG64(DM, TX)                                                                                                          \
+    hipLaunchKernelGGL((rr_glm_grad_t64_kernel<DM, TX>), grid, dim3(256), 0, c->stream, (const TX *)dX, N, ldx, fm->P + col0,    \
+                       fm->U + col0, fm->ld, n, d, Tdst, (int)rpb, tdet)
+#define RR_GG64D(DM)                           \
+    if (x_dtype == RR_F32) RR_GG64(DM, float); \
+    else RR_GG64(DM, double)
+    switch (dpad) {
+        case 8: RR_GG64D(8); break;
+        case 16: RR_GG64D(16); break;
+        case 32: RR_GG64D(32); break;
+        case 64: RR_GG64D(64); break;
+        default: RR_GG64D(128); break;
+    }
+#undef RR_GG64D
+#undef RR_GG64
+    RR_CHECK_HIP(hipGetLastError());
+    return tdet ? rr_det_reduce(c, Tdst, grid.y, tcount, tcount, dT) : RR_OK;
+}
+
 extern "C" {
 
 int rr_glm64_plan(int64_t rows, int64_t F, int KL, int num_cu, int64_t out[4]) {
@@ -479,40 +661,22 @@ int rr_featmat64_glm_rff(rr_featmat64 *fm, rr_basis *b, const void *dX, int x_dt
     RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_featmat64_glm_rff: bad dtype");
     RR_REQUIRE(col0 >= 0 && col0 + 2 * (int64_t)b->n <= fm->F, "rr_featmat64_glm_rff: columns out of range");
     RR_REQUIRE(ldx >= b->dpad && !b->large, "rr_featmat64_glm_rff: device X needs ldx >= rr_rff_padded_dim() = %d, Xdim <= 128", b->dpad);
-    rr_ctx *c = fm->ctx;
-    RR_CHECK_HIP(hipSetDevice(c->device));
-    const int n = b->n;
-    const int64_t N = fm->rows;
-    const int fblocks = (n + 255) / 256;
-    int64_t rpb = (N * fblocks + (int64_t)c->num_cu * 8 - 1) / ((int64_t)c->num_cu * 8);
-    if (rpb < 64) rpb = 64;
-    if ((N + rpb - 1) / rpb > 65535) rpb = (N + 65534) / 65535;
-    const dim3 grid(fblocks, (unsigned)((N + rpb - 1) / rpb));
-    const int64_t tcount = (int64_t)b->d * n, tdet = c->deterministic ? tcount : 0;
-    double *Tdst = dT;
-    if (tdet) {
-        void *part = nullptr;
-        int rc = rr_det_scratch(c, (size_t)grid.y * (size_t)tcount * 8, &part);
-        if (rc != RR_OK) return rc;
-        Tdst = (double *)part;
-    }
-#define RR_GG64(DM, TX)                                                                                                          \
-    hipLaunchKernelGGL((rr_glm_grad_t64_kernel<DM, TX>), grid, dim3(256), 0, c->stream, (const TX *)dX, N, ldx, fm->P + col0,    \
-                       fm->U + col0, fm->ld, n, b->d, Tdst, (int)rpb, tdet)
-#define RR_GG64D(DM)                           \
-    if (x_dtype == RR_F32) RR_GG64(DM, float); \
-    else RR_GG64(DM, double)
-    switch (b->dpad) {
-        case 8: RR_GG64D(8); break;
-        case 16: RR_GG64D(16); break;
-        case 32: RR_GG64D(32); break;
-        case 64: RR_GG64D(64); break;
-        default: RR_GG64D(128); break;
-    }
-#undef RR_GG64D
-#undef RR_GG64
-    RR_CHECK_HIP(hipGetLastError());
-    return tdet ? rr_det_reduce(c, Tdst, grid.y, tcount, tcount, dT) : RR_OK;
+    return glm64_grad_t(fm, dX, x_dtype, ldx, b->d, b->dpad, b->n, col0, dT);
+}
+
+// The same contraction against EdPhi for any trig block pair at [col0, col0 + 2n) and rows of 1 <= d <= 4096 columns, without a
+// random Fourier handle (rr_featmat64_pass2_xt's twin: the register kernel up to 128 columns, the float64 GEMM above)
+int rr_featmat64_glm_xt(rr_featmat64 *fm, const void *dX, int x_dtype, int64_t ldx, int d, int n, int64_t col0, double *dT) {
+    RR_REQUIRE(fm != nullptr && fm->U != nullptr && fm->have_edphi, "rr_featmat64_glm_xt: call rr_featmat64_glm_step first");
+    RR_REQUIRE(dT != nullptr && n >= 1, "rr_featmat64_glm_xt: bad argument");
+    RR_REQUIRE(d >= 1 && d <= RR_FM64_XT_MAX_DIM, "rr_featmat64_glm_xt: needs 1 <= Xdim <= %d, got %d", RR_FM64_XT_MAX_DIM, d);
+    RR_REQUIRE(x_dtype == RR_F32 || x_dtype == RR_F64, "rr_featmat64_glm_xt: bad dtype");
+    RR_REQUIRE(col0 >= 0 && col0 + 2 * (int64_t)n <= fm->F, "rr_featmat64_glm_xt: columns out of range");
+    const int dpad = rr_fm64_xt_dpad(d);
+    RR_REQUIRE(ldx >= dpad, "rr_featmat64_glm_xt: device X needs ldx >= %d for Xdim = %d", dpad, d);
+    RR_REQUIRE(dX != nullptr, "rr_featmat64_glm_xt: null X");
+    if (d > 128) return rr_fm64_xt_wide(fm, true, dX, x_dtype, ldx, d, n, col0, dT);
+    return glm64_grad_t(fm, dX, x_dtype, ldx, d, dpad, n, col0, dT);
 }
 
 int rr_featmat64_glm_edphi(rr_featmat64 *fm, int64_t col0, int64_t ncols, double *E) {

@@ -258,7 +258,17 @@ struct rr_featmat64 {
     // step clears have_rows, so neither side ever consumes what the other left there
     void *glm = nullptr;
     bool have_edphi = false;
+    // the wide contraction T = X^T A of rr_featmat64_pass2_xt / _glm_xt (d > 128, rr_glm64.hip): staged X panel and the GEMM's
+    // slab outputs, grow-only, freed with the second pass' scratch (A itself lives in Pt, free once U is formed)
+    double *xt = nullptr;
+    size_t xt_elems = 0;
 };
+// T (d, n) += X^T A for the trig block pair at [col0, col0 + 2n), 128 < d <= 4096, on the float64 GEMM (rr_glm64.hip); glm: A from
+// the stored EdPhi, else from the second pass' rows.  The caller has made every check.
+#define RR_FM64_XT_MAX_DIM RR_FEATMAT64_XT_MAX_DIM   // the FastFood chain's widest input
+// the leading dimension the contraction's X needs: whole padded rows for the register kernel (d <= 128), d itself above
+inline int rr_fm64_xt_dpad(int d) { return d <= 128 ? rr_pick_dmax(d) : d; }
+int rr_fm64_xt_wide(rr_featmat64 *fm, bool glm, const void *dX, int x_dtype, int64_t ldx, int d, int n, int64_t col0, double *dT);
 int rr_fm64_claim(rr_featmat64 *fm, int64_t col0, int64_t width, const char *who);  // rr_elbo.hip
 int rr_fm64_scratch(rr_featmat64 *fm);   // rr_elbo.hip: the second pass' scratch (Pt, U, ...), allocated on first use
 void rr_glm64_scratch_free(void *p);     // rr_glm64.hip

@@ -159,9 +159,10 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         cores, the likelihood terms and every sum in float64, in a fixed order), targets and the binomial's n are staged as
         float64, the reference's draws stay float64, and ``_sample_matrix`` projects in float64 -- a seeded fit reproduces
         the reference's to ~1e-9 instead of ~1e-4.  The basis children's own ``dtype`` does not matter: the float64 matrix
-        evaluates random Fourier, centre and polynomial children in float64 (the latter two as device children under
-        ``resident_bases="all"``); FastFood children and inputs of more than 128 columns go through their own ``transform``
-        in their own arithmetic.  ``fit`` takes the host loop around ``_elbo``, one library call per step; the look-ahead
+        evaluates random Fourier, centre, polynomial and FastFood children in float64 (all but the first as device children
+        under ``resident_bases="all"``: FastFoodRBF / FastFoodGM through the chain's float64 kernels, inputs up to 4096 columns);
+        by default FastFood children, and random Fourier inputs of more than 128 columns always, go through their own
+        ``transform`` in their own arithmetic.  ``fit`` takes the host loop around ``_elbo``, one library call per step; the look-ahead
         stages of the f32 pipeline (draws, uploads and gathers made a step ahead on worker threads) are left out in this mode:
         batch, draws and step follow each other on the calling thread, in the reference's order.  Refused with ValueError at
         ``fit``, before any device call: ``sampler="device"``, ``devices=``, ``distributed=True``, ``predict_engine="device"``,
