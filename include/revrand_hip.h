@@ -679,6 +679,29 @@ int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *chil
                        int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
                        const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
                        rr_glm_sviw **out);
+/* Spectral-mixture components (FastFoodGM, basis_functions.py:1386-1562) in the wide loop: three entry points beside the three
+ * above, as rr_glm_svi_create_gm sits beside rr_glm_svi_create.  The three above refuse RR_SGD_CHILD_GM exactly as before.
+ * rr_glm_sviwgm_create -- same arguments, same object (run, starts, read, destroy are rr_glm_sviw_'s) -- takes RR_SGD_CHILD_RFF,
+ * _LINEAR and _GM; any other kind: RR_ERR_INVALID naming the child.  A GM child is rr_glm_svi_create_gm's: basis = the dense
+ * random Fourier equivalent V (Xdim, n) of the component's chain (an RR_KIND_RFF handle of `ctx`), Xdim <= 128, n_ls = 2 Xdim slots
+ * [mean | length scales]; 4 n columns cos(a + b) | sin(a + b) | cos(a - b) | sin(a - b), a = x . (V[:, j] / l), b = x . mean, scaled
+ * by 1 / sqrt(2 n) -- the reference's column order (:1471-1473).  Another basis, another context's handle, Xdim > 128 or
+ * n_ls != 2 Xdim: RR_ERR_INVALID with a message naming the child.  A GM item owns frequencies [j0, j0 + count) and all FOUR their
+ * columns; with T+- = EdPhi_sin+- o Phi_cos+- - EdPhi_cos+- o Phi_sin+- per item and component, slot mean_i sums x_ri (T- - T+)[r][j]
+ * and slot l_i sums V[i][j] x_ri (T+ + T-)[r][j] / l_i^2 (:1477-1537), the partials added in item order like every other sum.
+ * rr_glm_sviwgm_plan: as rr_glm_sviw_plan, kind[c] also RR_SGD_CHILD_GM with n[c] = the component's frequencies (4 n columns) and
+ * d[c] = Xdim; the GM width is the largest count <= 32 that fits the LDS budget (RR_SVIW_ITEM replaces that cap too);
+ * info = (items, width, LDS bytes of the largest item, LDS budget, GM width).
+ * rr_glm_sviwgm_supported (no device needed): gm_cols = the sum of 4 n over the GM children; with gm_cols == 0 exactly
+ * rr_glm_sviw_supported. */
+int rr_glm_sviwgm_supported(int F, int K, int L, int M, int n_children, int dsum, int n_ls, int gm_cols);
+int rr_glm_sviwgm_plan(int n_children, const int *kind, const int *n, const int *d, int K, int L, int M, int cap, int *items,
+                       int64_t info[5]);
+int rr_glm_sviwgm_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                         const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K,
+                         int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
+                         const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
+                         rr_glm_sviw **out);
 /* As their rr_glm_svi_ namesakes.  run queues steps x (A, B, C, D) and returns; starts queues (A, B, D) per candidate back to
  * back and synchronises once. */
 int rr_glm_sviw_set_start(rr_glm_sviw *s, const double *z0, const double *lower, const double *upper, const unsigned char *is_log);

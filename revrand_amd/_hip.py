@@ -249,6 +249,14 @@ SIGNATURES = {
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                           ctypes.c_int64, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]),
+    "rr_glm_sviwgm_supported": (ctypes.c_int, [ctypes.c_int] * 8),
+    "rr_glm_sviwgm_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    "rr_glm_sviwgm_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_int64, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]),
     "rr_glm_sviw_set_start": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rr_glm_sviw_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                        ctypes.c_uint64]),
@@ -1506,14 +1514,15 @@ class FusedSvi(object):
 class WideSvi(FusedSvi):
     """The same loop for wide bases: a fixed chain of four kernels per step, many steps queued per call (rr_glm_sviw,
     rr_svi_wide.hip).  FusedSvi's arguments and its five methods; children: "rff" and "linear" tuples only (anything else is
-    refused by rr_glm_sviw_create with a message naming the child)."""
+    refused by rr_glm_sviw_create with a message naming the child).  gm_children=True selects rr_glm_sviwgm_create, which takes
+    FusedSvi's ("gm", RffHandle of the component's dense equivalent, 2 Xdim, dX) children too; all_children has no wide loop."""
 
     _prefix = "rr_glm_sviw_"
 
     def _creator(self, all_children, gm_children):
-        if all_children or gm_children:
-            raise ValueError("the wide loop takes random Fourier and linear children only")
-        return self.lib.rr_glm_sviw_create
+        if all_children:
+            raise ValueError("the wide loop takes random Fourier, spectral-mixture (gm_children=True) and linear children only")
+        return self.lib.rr_glm_sviwgm_create if gm_children else self.lib.rr_glm_sviw_create
 
     def run(self, steps, didx, dE=None, seed=0, key0=0):
         """`steps` x (the chain of four kernels) queued on the context's stream (asynchronous)."""
@@ -1529,29 +1538,45 @@ def sviw_supported(F, K, L, M, n_children, dsum, n_ls):
     return bool(load_library().rr_glm_sviw_supported(int(F), int(K), int(L), int(M), int(n_children), int(dsum), int(n_ls)))
 
 
+def sviw_supported_gm(F, K, L, M, n_children, dsum, n_ls, gm_cols):
+    """rr_glm_sviwgm_supported: the range of WideSvi(..., gm_children=True); gm_cols = the columns of the spectral-mixture
+    children together (4 n each).  gm_cols = 0: sviw_supported."""
+    return bool(load_library().rr_glm_sviwgm_supported(int(F), int(K), int(L), int(M), int(n_children), int(dsum), int(n_ls),
+                                                       int(gm_cols)))
+
+
 def sviw_plan(children, K, L, M):
     """rr_glm_sviw_plan (host only): the work items of one step of the wide loop.  children: ("rff", n frequencies, Xdim) |
     ("linear", columns of X, onescol) in concatenation order.  Returns (items, info): items a list of (child, first frequency or
-    column, count), info a dict with the item width in frequencies, the LDS bytes of the largest item and the budget."""
+    column, count), info a dict with the item width in frequencies, the LDS bytes of the largest item and the budget.
+    With a ("gm", n frequencies, Xdim) child among them (a spectral-mixture component: 4 n columns) the plan is
+    rr_glm_sviwgm_plan's and info["gm_width"] the width of a spectral-mixture item in frequencies."""
     lib = load_library()
     nk = len(children)
     kind, n, d = (ctypes.c_int * nk)(), (ctypes.c_int * nk)(), (ctypes.c_int * nk)()
     for i, ch in enumerate(children):
         if ch[0] == "rff":
             kind[i], n[i], d[i] = 0, int(ch[1]), int(ch[2])
+        elif ch[0] == "gm":
+            kind[i], n[i], d[i] = SGD_CHILD_KINDS["gm"], int(ch[1]), int(ch[2])
         elif ch[0] == "linear":
             kind[i], n[i], d[i] = 1, int(ch[1]) + (1 if ch[2] else 0), int(ch[1])
         else:
             raise ValueError("sviw_plan: child %d: %r is not taken by the wide loop" % (i, ch[0]))
-    info = (ctypes.c_int64 * 4)()
-    _check(lib, lib.rr_glm_sviw_plan(nk, ctypes.cast(kind, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p),
-                                     ctypes.cast(d, ctypes.c_void_p), int(K), int(L), int(M), 0, None, info))
+    gm = any(ch[0] == "gm" for ch in children)
+    plan = lib.rr_glm_sviwgm_plan if gm else lib.rr_glm_sviw_plan
+    info = (ctypes.c_int64 * 5)()
+    _check(lib, plan(nk, ctypes.cast(kind, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p),
+                     ctypes.cast(d, ctypes.c_void_p), int(K), int(L), int(M), 0, None, info))
     cap = int(info[0])
     items = (ctypes.c_int * (3 * cap))()
-    _check(lib, lib.rr_glm_sviw_plan(nk, ctypes.cast(kind, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p),
-                                     ctypes.cast(d, ctypes.c_void_p), int(K), int(L), int(M), cap, ctypes.cast(items, ctypes.c_void_p), info))
+    _check(lib, plan(nk, ctypes.cast(kind, ctypes.c_void_p), ctypes.cast(n, ctypes.c_void_p),
+                     ctypes.cast(d, ctypes.c_void_p), int(K), int(L), int(M), cap, ctypes.cast(items, ctypes.c_void_p), info))
     out = [(items[3 * i], items[3 * i + 1], items[3 * i + 2]) for i in range(cap)]
-    return out, {"items": cap, "width": int(info[1]), "lds_bytes": int(info[2]), "lds_budget": int(info[3])}
+    res = {"items": cap, "width": int(info[1]), "lds_bytes": int(info[2]), "lds_budget": int(info[3])}
+    if gm:
+        res["gm_width"] = int(info[4])
+    return out, res
 
 
 def svi_supported(F, K, L, M, n_children, dsum, n_ls):

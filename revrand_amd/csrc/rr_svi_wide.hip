@@ -5,7 +5,8 @@
 // does not grow.  Here NO workgroup ever waits for another: a step is a fixed chain of FOUR kernels on the context's stream
 // and the kernel boundary is the only ordering between workgroups; `steps` chains are queued per library call.  The basis is
 // cut into ITEMS (rr_glm_sviw_plan: a run of frequencies of one random Fourier child with BOTH their columns, or one whole
-// linear child), and every sum over the basis is "each (item, component) workgroup stores its partial, a later kernel adds
+// linear child; rr_glm_sviwgm_plan: also a run of frequencies of one spectral-mixture component with all FOUR their columns),
+// and every sum over the basis is "each (item, component) workgroup stores its partial, a later kernel adds
 // the partials in item order": no floating-point atomics, the same bits every run and for every cut of a fit into calls.
 //
 //   A  grid (items, K)   mk, sk of the item's columns; the minibatch rows gathered by index; Phi of the item (component 0's
@@ -37,6 +38,8 @@
 #define SW_THREADS 512
 #define SW_WAVES (SW_THREADS / 64)
 #define SW_ITEM_DEFAULT 64                   // frequencies per item at most (LDS permitting)
+#define SW_ITEM_GM_DEFAULT 32                // ... of a spectral-mixture component: 4 columns each, the same 128 columns per item
+#define SW_MAXLS (2 * SW_MAXD)               // slots of one child at most: a spectral-mixture component's [mean | length scales]
 #define SW_LDS_BUDGET (156 * 1024)           // what an item may take of a CU's 160 KiB
 #define SW_SCRATCH_MAX ((int64_t)2 << 30)    // the partials of fs (items K L M doubles) stay below this
 #define SW_LAUNCHES_PER_STEP 4
@@ -48,11 +51,11 @@ struct SwChild {
     int kind, col0, width, d, n, n_ls, ls0, onescol, x_f64, item0, nitems;
     const void *X;
     int64_t ldx;
-    const double *W;   // RFF: raw (d, n) row-major on the device
+    const double *W;   // RFF: raw (d, n) row-major on the device; GM: the dense equivalent V of the component's chain, likewise
 };
 
 struct SwItem {
-    int child, j0, cnt;   // RFF: frequencies [j0, j0 + cnt) and both their columns; linear: columns [j0, j0 + cnt) = all of them
+    int child, j0, cnt;   // RFF: frequencies [j0, j0 + cnt) and both their columns (GM: all four); linear: columns [j0, j0 + cnt) = all
 };
 
 struct SwArgs {
@@ -186,25 +189,32 @@ __device__ __forceinline__ double sw_update(const SwArgs &a, double zz, double g
 // ---- what one item holds in LDS (doubles) in kernel A (stage 0) and kernel C (stage 1) -----------------------------------------
 // A: the gathered rows, W / (2 pi l), Phi, mk, sk, the draws.  C: the same front part (W raw) plus dfs, Q, T, D_r, q, log z,
 // alpha; a linear item of C keeps neither draws nor Q (each draw is used once there: read or made on the fly).
+// rff: the column PAIRS [cos | sin] a frequency has -- 0 a linear item, 1 a random Fourier item, 2 a spectral-mixture item
+// (cos+ | sin+ | cos- | sin-: w = 4 cnt), which adds mean / (2 pi) (d), the rows' b = x . mean / (2 pi) (M) and a second T.
 struct SwLay {
-    size_t Xb, Wl, Phi, mk, sk, Ef, dfs, Q, T, Dr, q, logz, alpha, red, total;
+    size_t Xb, Wl, mu, bb, Phi, mk, sk, Ef, dfs, Q, T, Dr, q, logz, alpha, red, total;
     int w, wp;
 };
 
+// GM: the instance with spectral-mixture items (rff may be 2).  The kernels are instantiated twice on it: a fit without such a
+// child launches the <false> instances, whose code is what it was before these items existed.
+template <bool GM>
 static __host__ __device__ SwLay sw_layout(int rff, int cnt, int d, int K, int L, int M, int stage) {
     SwLay s;
-    s.w = rff ? 2 * cnt : cnt;
+    s.w = rff ? (GM ? 2 * rff * cnt : 2 * cnt) : cnt;
     s.wp = s.w | 1;   // odd row length of Phi: rows r, r + 1 of one column sit in different banks
     size_t o = 0;
     s.Xb = o; o += rff ? (size_t)M * d : 0;
     s.Wl = o; o += rff ? (size_t)d * cnt : 0;
+    s.mu = o; o += (GM && rff == 2) ? d : 0;
+    s.bb = o; o += (GM && rff == 2) ? M : 0;
     s.Phi = o; o += (size_t)M * s.wp;
     s.mk = o; o += s.w;
     s.sk = o; o += s.w;
     s.Ef = o; o += (rff || stage == 0) ? ((size_t)L * s.w + 1) / 2 : 0;
     s.dfs = o; o += stage ? (size_t)L * M : 0;
     s.Q = o; o += (stage && rff) ? (size_t)M * s.w : 0;
-    s.T = o; o += (stage && rff) ? (size_t)M * cnt : 0;
+    s.T = o; o += (stage && rff) ? (size_t)(GM ? rff : 1) * M * cnt : 0;
     s.Dr = o; o += stage ? M : 0;
     s.q = o; o += stage ? (size_t)K * K : 0;
     s.logz = o; o += stage ? K : 0;
@@ -215,34 +225,41 @@ static __host__ __device__ SwLay sw_layout(int rff, int cnt, int d, int K, int L
 }
 
 static size_t sw_item_bytes(int rff, int cnt, int d, int K, int L, int M) {
-    return 8 * std::max(sw_layout(rff, cnt, d, K, L, M, 0).total, sw_layout(rff, cnt, d, K, L, M, 1).total);
+    return 8 * std::max(sw_layout<true>(rff, cnt, d, K, L, M, 0).total, sw_layout<true>(rff, cnt, d, K, L, M, 1).total);
 }
 
 // the item's local column cc (< w) in the concatenation
+template <bool GM>
 __device__ __forceinline__ int sw_col(const SwChild &c, const SwItem &it, int cc) {
     if (c.kind == RR_SGD_CHILD_RFF) return c.col0 + (cc < it.cnt ? it.j0 + cc : c.n + it.j0 + (cc - it.cnt));
+    if (GM && c.kind == RR_SGD_CHILD_GM) return c.col0 + (cc / it.cnt) * c.n + it.j0 + cc % it.cnt;   // block cc / cnt of cos+ | sin+ | cos- | sin-
     return c.col0 + it.j0 + cc;
 }
 
+template <bool GM>
 __device__ __forceinline__ void sw_check_item(const SwArgs &a, const SwChild &c, const SwItem &it) {
+    RR_DEV_ASSERT(GM || c.kind != RR_SGD_CHILD_GM);
     RR_DEV_ASSERT(it.child >= 0 && it.child < a.nkids && it.cnt >= 1 && it.j0 >= 0);
     RR_DEV_ASSERT(c.col0 >= 0 && c.col0 + c.width <= a.F);
-    RR_DEV_ASSERT(c.kind == RR_SGD_CHILD_RFF ? (it.j0 + it.cnt <= c.n && c.width == 2 * c.n) : (it.j0 == 0 && it.cnt == c.width));
+    RR_DEV_ASSERT(c.kind == RR_SGD_CHILD_RFF ? (it.j0 + it.cnt <= c.n && c.width == 2 * c.n)
+                  : c.kind == RR_SGD_CHILD_GM ? (it.j0 + it.cnt <= c.n && c.width == 4 * c.n && c.n_ls == 2 * c.d)
+                                              : (it.j0 == 0 && it.cnt == c.width));
     RR_DEV_ASSERT(c.ls0 >= 0 && c.ls0 + c.n_ls <= a.n_ls && c.n_ls <= a.maxls);
 }
 
 // the item's draws of component k into LDS (L, w): the caller's or the device generator's -- the counter of rr_glm_draw_kernel
+template <bool GM>
 __device__ __forceinline__ void sw_draws(const SwArgs &a, const SwChild &c, const SwItem &it, int k, int w, ldsf *Ef) {
     const int tid = threadIdx.x, L = a.L, F = a.F;
     for (int o = tid; o < L * w; o += SW_THREADS) {
-        const int l = o / w, col = sw_col(c, it, o % w);
+        const int l = o / w, col = sw_col<GM>(c, it, o % w);
         RR_DEV_ASSERT(col >= c.col0 && col < c.col0 + c.width);
         const uint64_t ctr = ((uint64_t)k * (uint64_t)L + (uint64_t)l) * (uint64_t)F + (uint64_t)col;
         Ef[o] = a.E ? a.E[ctr] : sw_draw(a.stepkey, ctr);
     }
 }
 
-// the minibatch's rows of a random Fourier child's columns of X into LDS (M, d)
+// the minibatch's rows of a random Fourier (or spectral-mixture) child's columns of X into LDS (M, d)
 __device__ __forceinline__ void sw_gather(const SwArgs &a, const SwChild &c, ldsd *Xb) {
     for (int e = threadIdx.x; e < a.M * c.d; e += SW_THREADS) {
         const int r = e / c.d, i = e % c.d;
@@ -253,6 +270,7 @@ __device__ __forceinline__ void sw_gather(const SwArgs &a, const SwChild &c, lds
 }
 
 // ---- A ------------------------------------------------------------------------------------------------------------------
+template <bool GM>
 __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_a_kernel(const SwArgs a) {
 #pragma clang fp contract(off)
     extern __shared__ double sm[];
@@ -261,9 +279,9 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_a_kernel(const SwArgs 
     RR_DEV_ASSERT(ii < a.nitems && k < K);
     const SwItem it = a.items[ii];
     const SwChild &c = a.kid[it.child];
-    sw_check_item(a, c, it);
-    const bool rff = c.kind == RR_SGD_CHILD_RFF;
-    const SwLay s = sw_layout(rff, it.cnt, c.d, K, L, M, 0);
+    sw_check_item<GM>(a, c, it);
+    const bool rff = c.kind == RR_SGD_CHILD_RFF, gm = GM && c.kind == RR_SGD_CHILD_GM;
+    const SwLay s = sw_layout<GM>(gm ? 2 : rff, it.cnt, c.d, K, L, M, 0);
     const int w = s.w, wp = s.wp, cnt = it.cnt;
     ldsd *b = (ldsd *)sm;
     ldsd *Xb = b + s.Xb, *Wl = b + s.Wl, *Phi = b + s.Phi, *mk = b + s.mk, *sk = b + s.sk;
@@ -271,7 +289,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_a_kernel(const SwArgs 
     const int64_t fk = (int64_t)F * K;
     const double *xm = a.xin, *xC = a.xin + fk, *xs = a.xin + 2 * fk;
     for (int cc = tid; cc < w; cc += SW_THREADS) {
-        const int col = sw_col(c, it, cc);
+        const int col = sw_col<GM>(c, it, cc);
         mk[cc] = xm[(int64_t)col * K + k];
         sk[cc] = sqrt(xC[(int64_t)col * K + k]);
     }
@@ -283,10 +301,45 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_a_kernel(const SwArgs 
             const double l = xs[a.nkids + a.n_lik + c.ls0 + (c.n_ls == 1 ? 0 : i)];
             Wl[e] = c.W[(size_t)i * c.n + it.j0 + j] * (0.15915494309189533576888 / l);
         }
+    } else if (gm) {
+        // a spectral-mixture component (basis_functions.py:1386-1562): slots [mean (d) | length scales (d)], both per input dimension
+        ldsd *mu = b + s.mu;
+        const double *sl = xs + a.nkids + a.n_lik + c.ls0;
+        sw_gather(a, c, Xb);
+        for (int e = tid; e < c.d * cnt; e += SW_THREADS) {
+            const int i = e / cnt, j = e % cnt;
+            Wl[e] = c.W[(size_t)i * c.n + it.j0 + j] * (0.15915494309189533576888 / sl[c.d + i]);
+        }
+        for (int i = tid; i < c.d; i += SW_THREADS) mu[i] = 0.15915494309189533576888 * sl[i];
     }
-    sw_draws(a, c, it, k, w, Ef);
+    sw_draws<GM>(a, c, it, k, w, Ef);
     __syncthreads();
-    if (rff) {
+    if (gm) {
+        // b[r] = x_r . mean / (2 pi) ONCE per row, then cos(a + b) | sin(a + b) | cos(a - b) | sin(a - b), each / sqrt(2 n), with
+        // a = x_r . V[:, j] / (2 pi l): the reference's column order (:1471-1473), rr_svi.hip's arithmetic (svi_features)
+        ldsd *mu = b + s.mu, *bb = b + s.bb;
+        for (int r = tid; r < M; r += SW_THREADS) {
+            double t = 0.0;
+            for (int i = 0; i < c.d; ++i) t = fma(Xb[r * c.d + i], mu[i], t);
+            bb[r] = t;
+        }
+        __syncthreads();
+        const double scale = 1.0 / sqrt(2.0 * (double)c.n);
+        for (int e = tid; e < M * cnt; e += SW_THREADS) {
+            const int r = e / cnt, j = e % cnt;
+            double t = 0.0;
+            for (int i = 0; i < c.d; ++i) t = fma(Xb[r * c.d + i], Wl[i * cnt + j], t);
+            ldsd *ph = Phi + r * wp + j;
+            const double br = bb[r];
+#pragma unroll 1
+            for (int sg = 0; sg < 2; ++sg, ph += 2 * cnt) {   // the + pair, then the - pair (one copy of the sincos code)
+                double sn, cs;
+                rr_sincos_rev_f64(sg ? t - br : t + br, sn, cs);
+                ph[0] = cs * scale;
+                ph[cnt] = sn * scale;
+            }
+        }
+    } else if (rff) {
         const double scale = 1.0 / sqrt((double)c.n);
         for (int e = tid; e < M * cnt; e += SW_THREADS) {
             const int r = e / cnt, j = e % cnt;
@@ -308,7 +361,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_a_kernel(const SwArgs 
     }
     __syncthreads();
     if (k == 0)   // Phi does not depend on the component: kernel C reads it back instead of forming it again
-        for (int e = tid; e < M * w; e += SW_THREADS) a.Phi[(size_t)(e / w) * F + sw_col(c, it, e % w)] = Phi[(e / w) * wp + e % w];
+        for (int e = tid; e < M * w; e += SW_THREADS) a.Phi[(size_t)(e / w) * F + sw_col<GM>(c, it, e % w)] = Phi[(e / w) * wp + e % w];
     // the item's partial of fs[k, l, r] = sum_col (m + sqrt(C) e)[l][col] Phi[r][col]
     double *fsp = a.fsp + ((size_t)ii * K + k) * L * M;
     for (int o = tid; o < L * M; o += SW_THREADS) {
@@ -321,7 +374,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_a_kernel(const SwArgs 
     for (int l = wave; l < K; l += SW_WAVES) {
         double acc = 0.0;
         for (int cc = lane; cc < w; cc += 64) {
-            const int64_t col = sw_col(c, it, cc);
+            const int64_t col = sw_col<GM>(c, it, cc);
             const double dc = xC[col * K + k] + xC[col * K + l];
             const double dm = xm[col * K + k] - xm[col * K + l];
             acc += log(dc) + dm * dm / dc;
@@ -392,6 +445,7 @@ __device__ __forceinline__ void sw_logz(const SwArgs &a, const ldsd *q, ldsd *lo
 }
 
 // ---- C ------------------------------------------------------------------------------------------------------------------
+template <bool GM>
 __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs a) {
 #pragma clang fp contract(off)
     extern __shared__ double sm[];
@@ -400,9 +454,10 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs 
     RR_DEV_ASSERT(ii < a.nitems && k < K);
     const SwItem it = a.items[ii];
     const SwChild &c = a.kid[it.child];
-    sw_check_item(a, c, it);
-    const bool rff = c.kind == RR_SGD_CHILD_RFF;
-    const SwLay s = sw_layout(rff, it.cnt, c.d, K, L, M, 1);
+    sw_check_item<GM>(a, c, it);
+    // (rff: an item of [cos | sin] column pairs -- a random Fourier child's or, gm, a spectral-mixture component's two pairs)
+    const bool gm = GM && c.kind == RR_SGD_CHILD_GM, rff = gm || c.kind == RR_SGD_CHILD_RFF;
+    const SwLay s = sw_layout<GM>(gm ? 2 : rff, it.cnt, c.d, K, L, M, 1);
     const int w = s.w, wp = s.wp, cnt = it.cnt;
     ldsd *b = (ldsd *)sm;
     ldsd *Xb = b + s.Xb, *Wl = b + s.Wl, *Phi = b + s.Phi, *mk = b + s.mk, *sk = b + s.sk, *dfs = b + s.dfs, *Q = b + s.Q, *T = b + s.T,
@@ -412,16 +467,16 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs 
     const double *xm = a.xin, *xC = a.xin + fk, *xs = a.xin + 2 * fk;
     for (int o = tid; o < L * M; o += SW_THREADS) dfs[o] = a.dfs[(size_t)k * L * M + o];
     for (int cc = tid; cc < w; cc += SW_THREADS) {
-        const int col = sw_col(c, it, cc);
+        const int col = sw_col<GM>(c, it, cc);
         mk[cc] = xm[(int64_t)col * K + k];
         sk[cc] = sqrt(xC[(int64_t)col * K + k]);
     }
-    for (int e = tid; e < M * w; e += SW_THREADS) Phi[(e / w) * wp + e % w] = a.Phi[(size_t)(e / w) * F + sw_col(c, it, e % w)];
+    for (int e = tid; e < M * w; e += SW_THREADS) Phi[(e / w) * wp + e % w] = a.Phi[(size_t)(e / w) * F + sw_col<GM>(c, it, e % w)];
     for (int o = tid; o < K * K; o += SW_THREADS) q[o] = a.qf[o];
     if (rff) {
         sw_gather(a, c, Xb);
         for (int e = tid; e < c.d * cnt; e += SW_THREADS) Wl[e] = c.W[(size_t)(e / cnt) * c.n + it.j0 + e % cnt];
-        sw_draws(a, c, it, k, w, Ef);
+        sw_draws<GM>(a, c, it, k, w, Ef);
     }
     __syncthreads();
     sw_logz(a, q, logz);
@@ -450,7 +505,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs 
     double n2 = 0.0;
     for (int p = tid; p < 2 * w; p += SW_THREADS) {
         const int cov = p >= w, cc = cov ? p - w : p;
-        const int64_t col = sw_col(c, it, cc);
+        const int64_t col = sw_col<GM>(c, it, cc);
         double ed = 0.0;
         if (!cov) {
             for (int r = 0; r < M; ++r) ed = fma(Dr[r], Phi[r * wp + cc], ed);
@@ -495,6 +550,34 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs 
     n2 = sw_block_sum(n2, red);
     if (tid == 0) a.n2p[(size_t)ii * K + k] = n2;
     if (!rff) return;
+    if (gm) {
+        // T+-[r][j] = EdPhi_sin+- Phi_cos+- - EdPhi_cos+- Phi_sin+- over the + and the - pair of blocks; slot mean_i takes
+        // sum_{r, j} x_ri (T- - T+)[r][j], slot l_i sum_{r, j} V_ij x_ri (T+ + T-)[r][j] (the factor 1 / l_i^2 in kernel D): means first,
+        // then length scales -- rr_svi.hip's formulas for the component (basis_functions.py:1477-1537)
+        const double sc = 1.0 / ((double)L * K);
+        ldsd *Tp = T, *Tm = T + M * cnt;
+        for (int o = tid; o < 2 * M * cnt; o += SW_THREADS) {
+            const int blk = o / (M * cnt), e = o % (M * cnt), r = e / cnt, jc = 2 * blk * cnt + e % cnt, js = jc + cnt;
+            const double epc = (mk[jc] * Dr[r] + sk[jc] * Q[r * w + jc]) * sc;
+            const double eps = (mk[js] * Dr[r] + sk[js] * Q[r * w + js]) * sc;
+            T[o] = eps * Phi[r * wp + jc] - epc * Phi[r * wp + js];
+        }
+        __syncthreads();
+        for (int h = wave; h < 2 * c.d; h += SW_WAVES) {
+            const bool mean = h < c.d;
+            const int i = mean ? h : h - c.d;
+            RR_DEV_ASSERT(h < c.n_ls && c.ls0 + h < a.n_ls && h < a.maxls && i < c.d);
+            double acc = 0.0;
+            for (int o = lane; o < M * cnt; o += 64) {
+                const int r = o / cnt, j = o % cnt;
+                if (mean) acc = fma(Xb[r * c.d + i], Tm[o] - Tp[o], acc);
+                else acc = fma(Wl[i * cnt + j] * Xb[r * c.d + i], Tp[o] + Tm[o], acc);
+            }
+            acc = sw_wave_sum(acc);
+            if (lane == 0) a.glsp[((size_t)ii * K + k) * a.maxls + h] = acc;
+        }
+        return;
+    }
     // the item's share of -(EdPhi o dPhi_i).sum() of this component: W[i, :] . T[i, :] (the factor 1 / l_i^2 in kernel D) with
     // T = X^T (E_s o P_c - E_c o P_s), EdPhi[r][j] = (mk[j] D_r + sk[j] Q[r][j]) / (L K); the isotropic parameter takes input
     // dimension 0 only, as the reference does (basis_functions.py:896)
@@ -519,6 +602,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs 
 }
 
 // ---- D ------------------------------------------------------------------------------------------------------------------
+template <bool GM>
 __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_d_kernel(const SwArgs a) {
 #pragma clang fp contract(off)
     __shared__ double qm[SW_MAXK * SW_MAXK], logzm[SW_MAXK], llm[SW_MAXK], Rcm[SW_MAXCHILD], glsm[SW_MAXCHILD * SW_MAXD], redm[8];
@@ -555,6 +639,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_d_kernel(const SwArgs 
             while (ci + 1 < nk && !(h >= a.kid[ci].ls0 && h < a.kid[ci].ls0 + a.kid[ci].n_ls)) ++ci;
             const SwChild &c = a.kid[ci];
             const int i = h - c.ls0;
+            // (a spectral-mixture component's 2 d slots sit in glsp as they do in z: means, then length scales)
             RR_DEV_ASSERT(i >= 0 && i < c.n_ls && i < a.maxls && c.item0 >= 0 && c.item0 + c.nitems <= a.nitems);
             double acc = 0.0;
             for (int e = lane; e < K * c.nitems; e += 64)
@@ -581,6 +666,13 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_d_kernel(const SwArgs 
             } else {
                 const double l = xs[p];
                 g = gls[p - nk - a.n_lik] / (1.0 * (l * l));
+                if (GM) {   // the slot's factor is 1 / l^2 for a length scale, 1 for a spectral-mixture mean (any sign, never a divisor)
+                    const int h = p - nk - a.n_lik;
+                    bool mean = false;
+                    for (int ci = 0; ci < nk; ++ci)
+                        mean = mean || (a.kid[ci].kind == RR_SGD_CHILD_GM && h >= a.kid[ci].ls0 && h < a.kid[ci].ls0 + a.kid[ci].d);
+                    if (mean) g = gls[h];
+                }
             }
             const int64_t gi = 2 * fk + p;
             const bool lg = a.islog[gi] != 0;
@@ -624,21 +716,27 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_x_kernel(const double 
 
 // ---- the one place that decides the split -------------------------------------------------------------------------------
 // width: the largest count of frequencies <= SW_ITEM_DEFAULT (RR_SVIW_ITEM replaces that cap) whose item fits the LDS budget for
-// every random Fourier child; a linear child is one item whatever its width.  Returns the number of items, or -1 when an item
-// cannot fit (or a child is of another kind); items (cap triples) may be null.
-static int sw_plan(int n_children, const int *kind, const int *n, const int *d, int K, int L, int M, int cap, int *items, int64_t info[4]) {
-    int want = SW_ITEM_DEFAULT;
+// every random Fourier child; a linear child is one item whatever its width.  gmok (rr_glm_sviwgm_*): spectral-mixture children
+// too, cut the same way with a width of their own -- the largest count <= SW_ITEM_GM_DEFAULT (RR_SVIW_ITEM replaces that cap as
+// well) whose item fits for every such child.  Returns the number of items, or -1 when an item cannot fit (or a child is of
+// another kind); items (cap triples) may be null.  info: (items, width, worst item's bytes, budget, spectral-mixture width).
+static int sw_kind_pairs(int kind) { return kind == RR_SGD_CHILD_GM ? 2 : (kind == RR_SGD_CHILD_RFF ? 1 : 0); }
+
+static int sw_plan(int n_children, const int *kind, const int *n, const int *d, int K, int L, int M, int cap, int *items, int64_t info[5],
+                   bool gmok = false) {
+    int width = SW_ITEM_DEFAULT, gwidth = SW_ITEM_GM_DEFAULT;
     const char *env = getenv("RR_SVIW_ITEM");
-    if (env && atoi(env) >= 1) want = atoi(env);
-    int width = want;
+    if (env && atoi(env) >= 1) width = gwidth = atoi(env);
     size_t worst = 0;
     for (int c = 0; c < n_children; ++c) {
-        if (kind[c] == RR_SGD_CHILD_RFF) {
+        if (kind[c] == RR_SGD_CHILD_RFF || (gmok && kind[c] == RR_SGD_CHILD_GM)) {
             if (n[c] < 1 || d[c] < 1) return -1;
-            int wc = std::min(width, n[c]);
-            while (wc >= 1 && sw_item_bytes(1, wc, d[c], K, L, M) > SW_LDS_BUDGET) --wc;
+            const int pairs = sw_kind_pairs(kind[c]);
+            int &wd = pairs == 2 ? gwidth : width;
+            int wc = std::min(wd, n[c]);
+            while (wc >= 1 && sw_item_bytes(pairs, wc, d[c], K, L, M) > SW_LDS_BUDGET) --wc;
             if (wc < 1) return -1;
-            if (wc < std::min(width, n[c])) width = wc;
+            if (wc < std::min(wd, n[c])) wd = wc;
         } else if (kind[c] == RR_SGD_CHILD_LINEAR) {
             if (n[c] < 1 || sw_item_bytes(0, n[c], d[c], K, L, M) > SW_LDS_BUDGET) return -1;
         } else {
@@ -647,10 +745,10 @@ static int sw_plan(int n_children, const int *kind, const int *n, const int *d, 
     }
     int ni = 0;
     for (int c = 0; c < n_children; ++c) {
-        const bool rff = kind[c] == RR_SGD_CHILD_RFF;
-        for (int j0 = 0; j0 < n[c]; j0 += rff ? width : n[c]) {
-            const int cnt = rff ? std::min(width, n[c] - j0) : n[c];
-            worst = std::max(worst, sw_item_bytes(rff, cnt, d[c], K, L, M));
+        const int pairs = sw_kind_pairs(kind[c]), wd = pairs == 2 ? gwidth : width;
+        for (int j0 = 0; j0 < n[c]; j0 += pairs ? wd : n[c]) {
+            const int cnt = pairs ? std::min(wd, n[c] - j0) : n[c];
+            worst = std::max(worst, sw_item_bytes(pairs, cnt, d[c], K, L, M));
             if (items && ni < cap) {
                 items[3 * ni] = c;
                 items[3 * ni + 1] = j0;
@@ -664,6 +762,7 @@ static int sw_plan(int n_children, const int *kind, const int *n, const int *d, 
         info[1] = width;
         info[2] = (int64_t)worst;
         info[3] = SW_LDS_BUDGET;
+        info[4] = gwidth;
     }
     return ni;
 }
@@ -681,6 +780,7 @@ struct rr_glm_sviw {
     double *lower = nullptr, *upper = nullptr, *xbuf[2] = {nullptr, nullptr}, *objs = nullptr, *norms = nullptr;
     int64_t maxiter = 0, t = 0;
     size_t lds_bytes = 0;
+    bool gm = false;   // a spectral-mixture child among them: the kernels' <true> instances
     double *cand = nullptr, *out = nullptr;
     size_t cand_cap = 0, out_cap = 0;
 };
@@ -710,7 +810,7 @@ int rr_glm_sviw_supported(int F, int K, int L, int M, int n_children, int dsum, 
     // the widest child the inputs allow: one random Fourier child and one linear child over min(dsum, 128) columns must both fit
     const int d = std::max(1, std::min(dsum, SW_MAXD));
     const int kind[2] = {RR_SGD_CHILD_RFF, RR_SGD_CHILD_LINEAR}, n[2] = {std::max(1, F / 2), std::min(F, d + 1)}, dd[2] = {d, d};
-    int64_t info[4];
+    int64_t info[5];
     if (sw_plan(2, kind, n, dd, K, L, M, 0, nullptr, info) < 1) return 0;
     // the partials of fs: (items, K, L, M) doubles
     const int64_t items = (F / 2 + info[1] - 1) / info[1] + n_children;
@@ -725,6 +825,49 @@ int rr_glm_sviw_supported(int F, int K, int L, int M, int n_children, int dsum, 
     return 1.25 * wide_us <= step_us ? 1 : 0;
 }
 
+int rr_glm_sviwgm_supported(int F, int K, int L, int M, int n_children, int dsum, int n_ls, int gm_cols) {
+    if (gm_cols == 0) return rr_glm_sviw_supported(F, K, L, M, n_children, dsum, n_ls);
+    if (F < 1 || F > SW_MAXF || K < 1 || K > SW_MAXK || L < 1 || L > SW_MAXL || M < 1 || M > SW_MAXM) return 0;
+    if (n_children < 1 || n_children > SW_MAXCHILD || F < n_children || dsum < 0 || dsum > SW_MAXCHILD * SW_MAXD) return 0;
+    if (n_ls < 0 || n_ls > SW_MAXCHILD * SW_MAXD || gm_cols < 4 || gm_cols > F || gm_cols % 4) return 0;
+    // the widest children the inputs allow: one spectral-mixture component of all gm_cols columns, one random Fourier child of
+    // the rest and one linear child, each over min(dsum, 128) columns of X, must fit
+    const int d = std::max(1, std::min(dsum, SW_MAXD));
+    const int kind[3] = {RR_SGD_CHILD_GM, RR_SGD_CHILD_LINEAR, RR_SGD_CHILD_RFF};
+    const int n[3] = {gm_cols / 4, std::min(F, d + 1), std::max(1, (F - gm_cols) / 2)}, dd[3] = {d, d, d};
+    int64_t info[5];
+    if (sw_plan(F - gm_cols >= 2 ? 3 : 2, kind, n, dd, K, L, M, 0, nullptr, info, true) < 1) return 0;
+    const int64_t items = (gm_cols / 4 + info[4] - 1) / info[4] + ((F - gm_cols) / 2 + info[1] - 1) / info[1] + 2 * (int64_t)n_children;
+    if (items * K * L * M * 8 > SW_SCRATCH_MAX) return 0;
+    // The upper edge, as rr_glm_sviw_supported's: in range is what the chain wins by 1.25 x on a model fitted to the measured
+    // per-step times (docs/KERNELS.md 3.50: MI355X, K L = 500, Xdim = 4, one to eight components, F = 128 ... 4096, minibatches
+    // of 10, 32 and 64 rows).  Both sides err against the chain: its time ~58 + 0.0146 F + 2.5e-3 (M - 10) F us is the measured
+    // one at 10 rows up to F = 1024 and at 32 rows, and above it at F = 4096 (by 17 %) and at 64 rows (by 24 %); the F terms grow
+    // with K L beyond 500 and do not shrink below it (not measured).  The step-per-call loop took 125 + 16 per component +
+    // 0.035 F us or more at 10 rows and more at larger minibatches; the number of components is not known here, so ONE is
+    // assumed and the other columns are priced as random Fourier columns (3.48).  Every measured shape inside won by 2.5 x or more.
+    const double kl = std::max(1.0, (double)K * L / 500.0);
+    const double wide_us = 58.0 + (0.0146 * F + 2.5e-3 * (double)std::max(M - 10, 0) * F) * kl;
+    const double step_us = 141.0 + 0.025 * F + 0.010 * gm_cols;
+    return 1.25 * wide_us <= step_us ? 1 : 0;
+}
+
+int rr_glm_sviwgm_plan(int n_children, const int *kind, const int *n, const int *d, int K, int L, int M, int cap, int *items,
+                       int64_t info[5]) {
+    RR_REQUIRE(kind != nullptr && n != nullptr && d != nullptr && info != nullptr && n_children >= 1 && n_children <= SW_MAXCHILD &&
+               K >= 1 && K <= SW_MAXK && L >= 1 && M >= 1 && cap >= 0, "rr_glm_sviwgm_plan: bad argument");
+    for (int c = 0; c < n_children; ++c)
+        RR_REQUIRE(kind[c] == RR_SGD_CHILD_RFF || kind[c] == RR_SGD_CHILD_LINEAR || kind[c] == RR_SGD_CHILD_GM,
+                   "rr_glm_sviwgm_plan: child %d: kind %d is not taken by the wide loop (random Fourier, spectral-mixture and linear "
+                   "children only)", c, kind[c]);
+    if (sw_plan(n_children, kind, n, d, K, L, M, cap, items, info, true) < 1) {
+        rr_set_error("rr_glm_sviwgm_plan: no item of this shape fits %d bytes of LDS (K = %d, nsamples = %d, minibatch = %d)",
+                     SW_LDS_BUDGET, K, L, M);
+        return RR_ERR_UNSUPPORTED;
+    }
+    return RR_OK;
+}
+
 int rr_glm_sviw_plan(int n_children, const int *kind, const int *n, const int *d, int K, int L, int M, int cap, int *items,
                      int64_t info[4]) {
     RR_REQUIRE(kind != nullptr && n != nullptr && d != nullptr && info != nullptr && n_children >= 1 && n_children <= SW_MAXCHILD &&
@@ -732,7 +875,10 @@ int rr_glm_sviw_plan(int n_children, const int *kind, const int *n, const int *d
     for (int c = 0; c < n_children; ++c)
         RR_REQUIRE(kind[c] == RR_SGD_CHILD_RFF || kind[c] == RR_SGD_CHILD_LINEAR, "rr_glm_sviw_plan: child %d: kind %d is not taken by "
                    "the wide loop (random Fourier and linear children only)", c, kind[c]);
-    if (sw_plan(n_children, kind, n, d, K, L, M, cap, items, info) < 1) {
+    int64_t inf[5];
+    const int ni = sw_plan(n_children, kind, n, d, K, L, M, cap, items, inf);
+    for (int i = 0; i < 4; ++i) info[i] = ni < 1 ? 0 : inf[i];
+    if (ni < 1) {
         rr_set_error("rr_glm_sviw_plan: no item of this shape fits %d bytes of LDS (K = %d, nsamples = %d, minibatch = %d)",
                      SW_LDS_BUDGET, K, L, M);
         return RR_ERR_UNSUPPORTED;
@@ -740,11 +886,12 @@ int rr_glm_sviw_plan(int n_children, const int *kind, const int *n, const int *d
     return RR_OK;
 }
 
-int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
-                       const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K, int L,
-                       int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper, const unsigned char *is_log,
-                       int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_sviw **out) {
-    const char *who = "rr_glm_sviw_create";
+// gmok: rr_glm_sviwgm_create -- spectral-mixture children too; rr_glm_sviw_create refuses them as it always did
+static int sw_create(bool gmok, rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                     const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K, int L,
+                     int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper, const unsigned char *is_log,
+                     int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_sviw **out) {
+    const char *who = gmok ? "rr_glm_sviwgm_create" : "rr_glm_sviw_create";
     RR_REQUIRE(ctx != nullptr && children != nullptr && dX != nullptr && x_dtype != nullptr && ldx != nullptr && dy != nullptr &&
                z0 != nullptr && lower != nullptr && upper != nullptr && is_log != nullptr && upd_par != nullptr && out != nullptr,
                "%s: null argument", who);
@@ -757,16 +904,22 @@ int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *chil
     RR_REQUIRE(updater >= RR_UPD_SGD && updater <= RR_UPD_ADAM, "%s: unknown updater %d", who, updater);
     RR_REQUIRE(maxiter >= 1 && maxiter < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), "%s: bad maxiter / N", who);
     RR_REQUIRE(dtype == RR_F32 || dtype == RR_F64, "%s: bad dtype", who);
-    for (int s = 0; s < n_children; ++s)
-        RR_REQUIRE(children[s].kind == RR_SGD_CHILD_RFF || children[s].kind == RR_SGD_CHILD_LINEAR,
-                   "%s: child %d: kind %d is not taken by the wide loop (random Fourier and linear children only)", who, s, children[s].kind);
+    for (int s = 0; s < n_children; ++s) {
+        if (gmok)
+            RR_REQUIRE(children[s].kind == RR_SGD_CHILD_RFF || children[s].kind == RR_SGD_CHILD_LINEAR || children[s].kind == RR_SGD_CHILD_GM,
+                       "%s: child %d: kind %d is not taken by the wide loop (random Fourier, spectral-mixture and linear children only)",
+                       who, s, children[s].kind);
+        else
+            RR_REQUIRE(children[s].kind == RR_SGD_CHILD_RFF || children[s].kind == RR_SGD_CHILD_LINEAR,
+                       "%s: child %d: kind %d is not taken by the wide loop (random Fourier and linear children only)", who, s, children[s].kind);
+    }
     RR_CHECK_HIP(hipSetDevice(ctx->device));
     rr_glm_sviw *o = new rr_glm_sviw();
     o->ctx = ctx;
     SwArgs &a = o->a;
     memset(&a, 0, sizeof a);
     memset(o->hkid, 0, sizeof o->hkid);
-    int col = 0, nls = 0, dsum = 0, maxls = 1;
+    int col = 0, nls = 0, dsum = 0, maxls = 1, gm_cols = 0;
     int pk[SW_MAXCHILD], pn[SW_MAXCHILD], pd[SW_MAXCHILD];
     for (int s = 0; s < n_children; ++s) {
         const rr_glm_sgd_child &k = children[s];
@@ -778,12 +931,25 @@ int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *chil
         c.ldx = ldx[s];
         c.x_f64 = x_dtype[s] == RR_F64;
         bool ok = dX[s] != nullptr && (x_dtype[s] == RR_F32 || x_dtype[s] == RR_F64);
-        if (ok && k.kind == RR_SGD_CHILD_RFF) {
+        const bool gm = k.kind == RR_SGD_CHILD_GM;
+        if (gm) {   // rr_glm_svi_create_gm's child contract (basis_functions.py:1386-1562 through the chain's dense equivalent)
             rr_basis *b = k.basis;
-            ok = b != nullptr && b->kind == RR_KIND_RFF && b->ctx == ctx && b->d >= 1 && b->d <= SW_MAXD && b->n >= 1 &&
-                 (k.n_ls == 1 || k.n_ls == b->d) && (int)b->W.size() == b->d * b->n;
+            if (!(ok && b != nullptr && b->kind == RR_KIND_RFF && b->ctx == ctx && !b->large && b->d >= 1 && b->d <= SW_MAXD && b->n >= 1 &&
+                  k.n_ls == 2 * b->d && (int)b->W.size() == b->d * b->n)) {
+                sw_free(o);
+                rr_set_error("%s: child %d: a spectral-mixture child (RR_SGD_CHILD_GM) needs the dense random Fourier equivalent of its "
+                             "chain on this context, Xdim <= %d, n_ls = 2 Xdim coordinates [mean | length scales] (n_ls=%d, Xdim=%d) and "
+                             "its resident rows", who, s, SW_MAXD, k.n_ls, b != nullptr && b->kind == RR_KIND_RFF ? b->d : -1);
+                return RR_ERR_INVALID;
+            }
+        }
+        if (ok && (k.kind == RR_SGD_CHILD_RFF || gm)) {
+            rr_basis *b = k.basis;
+            ok = gm || (b != nullptr && b->kind == RR_KIND_RFF && b->ctx == ctx && b->d >= 1 && b->d <= SW_MAXD && b->n >= 1 &&
+                        (k.n_ls == 1 || k.n_ls == b->d) && (int)b->W.size() == b->d * b->n);
             if (ok) {
-                c.d = b->d; c.n = b->n; c.n_ls = k.n_ls; c.width = 2 * b->n; c.onescol = 0;
+                c.d = b->d; c.n = b->n; c.n_ls = k.n_ls; c.width = (gm ? 4 : 2) * b->n; c.onescol = 0;
+                gm_cols += gm ? c.width : 0;
                 double *w = nullptr;
                 if (hipMalloc((void **)&w, b->W.size() * 8) != hipSuccess ||
                     hipMemcpy(w, b->W.data(), b->W.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
@@ -821,16 +987,17 @@ int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *chil
     a.y = dy; a.rowarg = drowarg; a.lconst = dlconst; a.bmag = bmag;
     a.nbx = (L * M + SW_THREADS - 1) / SW_THREADS;
     for (int i = 0; i < 4; ++i) a.up[i] = upd_par[i];
-    int64_t info[4] = {0, 0, 0, 0};
-    const int ni = rr_glm_sviw_supported(a.F, K, L, M, n_children, dsum, nls) ? sw_plan(n_children, pk, pn, pd, K, L, M, 0, nullptr, info) : -1;
+    int64_t info[5] = {0, 0, 0, 0, 0};
+    const int ni = rr_glm_sviwgm_supported(a.F, K, L, M, n_children, dsum, nls, gm_cols)
+                       ? sw_plan(n_children, pk, pn, pd, K, L, M, 0, nullptr, info, gmok) : -1;
     if (ni < 1 || (int64_t)ni * K * L * M * 8 > 2 * SW_SCRATCH_MAX) {
         sw_free(o);
         rr_set_error("%s: F = %d, K = %d, nsamples = %d, minibatch = %d is outside the wide small-batch loop's range "
-                     "(rr_glm_sviw_supported)", who, a.F, K, L, M);
+                     "(%s)", who, a.F, K, L, M, gmok ? "rr_glm_sviwgm_supported" : "rr_glm_sviw_supported");
         return RR_ERR_UNSUPPORTED;
     }
     std::vector<int> items((size_t)3 * ni);
-    (void)sw_plan(n_children, pk, pn, pd, K, L, M, ni, items.data(), info);
+    (void)sw_plan(n_children, pk, pn, pd, K, L, M, ni, items.data(), info, gmok);
     std::vector<SwItem> hitems((size_t)ni);
     for (int s = 0; s < n_children; ++s) o->hkid[s].item0 = -1;
     for (int i = 0; i < ni; ++i) {
@@ -842,6 +1009,7 @@ int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *chil
         c.nitems = i - c.item0 + 1;
     }
     a.nitems = ni;
+    o->gm = gm_cols > 0;
     o->lds_bytes = (size_t)info[2];
     o->maxiter = maxiter;
     const size_t nb = (size_t)a.np * 8, nik = (size_t)ni * K;
@@ -878,8 +1046,10 @@ int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *chil
     if (e == hipSuccess) e = hipMemset(a.glsp, 0, nik * maxls * 8);
     if (e == hipSuccess) e = hipMemset(o->objs, 0, (size_t)maxiter * 8);
     if (e == hipSuccess) e = hipMemset(o->norms, 0, (size_t)maxiter * 8);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)rr_glm_sviw_a_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)rr_glm_sviw_c_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const void *dyn[2] = {o->gm ? (const void *)rr_glm_sviw_a_kernel<true> : (const void *)rr_glm_sviw_a_kernel<false>,
+                          o->gm ? (const void *)rr_glm_sviw_c_kernel<true> : (const void *)rr_glm_sviw_c_kernel<false>};
+    if (e == hipSuccess) e = hipFuncSetAttribute(dyn[0], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute(dyn[1], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -897,6 +1067,23 @@ int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *chil
     }
     *out = o;
     return RR_OK;
+}
+
+int rr_glm_sviw_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                       const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K, int L,
+                       int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper, const unsigned char *is_log,
+                       int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_sviw **out) {
+    return sw_create(false, ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dlconst, dtype, K, L, M, lik, n_lik, z0, lower,
+                     upper, is_log, updater, upd_par, maxiter, bmag, out);
+}
+
+int rr_glm_sviwgm_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *children, const void *const *dX, const int *x_dtype,
+                         const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst, int dtype, int K,
+                         int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
+                         const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag,
+                         rr_glm_sviw **out) {
+    return sw_create(true, ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dlconst, dtype, K, L, M, lik, n_lik, z0, lower,
+                     upper, is_log, updater, upd_par, maxiter, bmag, out);
 }
 
 int rr_glm_sviw_set_start(rr_glm_sviw *o, const double *z0, const double *lower, const double *upper, const unsigned char *is_log) {
@@ -937,10 +1124,17 @@ int rr_glm_sviw_run(rr_glm_sviw *o, int64_t steps, const int *d_idx, const float
         a.obj = o->objs + gt;
         a.norm = o->norms + gt;
         a.objective_only = 0;
-        hipLaunchKernelGGL(rr_glm_sviw_a_kernel, gi, th, o->lds_bytes, c->stream, a);
-        hipLaunchKernelGGL(rr_glm_sviw_b_kernel, gb, th, 0, c->stream, a);
-        hipLaunchKernelGGL(rr_glm_sviw_c_kernel, gi, th, o->lds_bytes, c->stream, a);
-        hipLaunchKernelGGL(rr_glm_sviw_d_kernel, dim3(1), th, 0, c->stream, a);
+        if (o->gm) {   // (the launch counters of the bounds build know an instance by the kernel's name alone)
+            hipLaunchKernelGGL(rr_glm_sviw_a_kernel<true>, gi, th, o->lds_bytes, c->stream, a);
+            hipLaunchKernelGGL(rr_glm_sviw_b_kernel, gb, th, 0, c->stream, a);
+            hipLaunchKernelGGL(rr_glm_sviw_c_kernel<true>, gi, th, o->lds_bytes, c->stream, a);
+            hipLaunchKernelGGL(rr_glm_sviw_d_kernel<true>, dim3(1), th, 0, c->stream, a);
+        } else {
+            hipLaunchKernelGGL(rr_glm_sviw_a_kernel<false>, gi, th, o->lds_bytes, c->stream, a);
+            hipLaunchKernelGGL(rr_glm_sviw_b_kernel, gb, th, 0, c->stream, a);
+            hipLaunchKernelGGL(rr_glm_sviw_c_kernel<false>, gi, th, o->lds_bytes, c->stream, a);
+            hipLaunchKernelGGL(rr_glm_sviw_d_kernel<false>, dim3(1), th, 0, c->stream, a);
+        }
     }
     RR_CHECK_HIP(hipGetLastError());
     o->t += steps;
@@ -980,9 +1174,15 @@ int rr_glm_sviw_starts(rr_glm_sviw *o, int ncand, const int *d_idx, const double
         a.obj = o->out + s;
         a.norm = nullptr;
         a.objective_only = 1;
-        hipLaunchKernelGGL(rr_glm_sviw_a_kernel, gi, th, o->lds_bytes, c->stream, a);
-        hipLaunchKernelGGL(rr_glm_sviw_b_kernel, gb, th, 0, c->stream, a);
-        hipLaunchKernelGGL(rr_glm_sviw_d_kernel, dim3(1), th, 0, c->stream, a);
+        if (o->gm) {
+            hipLaunchKernelGGL(rr_glm_sviw_a_kernel<true>, gi, th, o->lds_bytes, c->stream, a);
+            hipLaunchKernelGGL(rr_glm_sviw_b_kernel, gb, th, 0, c->stream, a);
+            hipLaunchKernelGGL(rr_glm_sviw_d_kernel<true>, dim3(1), th, 0, c->stream, a);
+        } else {
+            hipLaunchKernelGGL(rr_glm_sviw_a_kernel<false>, gi, th, o->lds_bytes, c->stream, a);
+            hipLaunchKernelGGL(rr_glm_sviw_b_kernel, gb, th, 0, c->stream, a);
+            hipLaunchKernelGGL(rr_glm_sviw_d_kernel<false>, dim3(1), th, 0, c->stream, a);
+        }
     }
     RR_CHECK_HIP(hipGetLastError());
     RR_CHECK_HIP(hipMemcpyAsync(objs_host, o->out, (size_t)ncand * 8, hipMemcpyDeviceToHost, c->stream));

@@ -152,7 +152,9 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         per component, 2 Xdim coordinates [mean | length scales] -- whenever the shape is in range (rr_glm_svi_supported_gm).
         Under this value a FastFoodGM child of Xdim <= 8, which the chain kernel's mixture mode does not serve, stays resident
         through that dense equivalent (rr_featmat_put_gm), so such a fit has the step-per-call loop as well: out of range,
-        between ranks or with minibatches split over ``devices=``.  Any other value: ValueError at ``fit``.
+        between ranks or with minibatches split over ``devices=``.  Together with ``wide_fused=True`` a shape this kernel
+        declines -- at K = 10 and 50 samples every mixture above D = 200 -- takes the wide loop instead (see there).  Any other
+        value: ValueError at ``fit``.
     dtype : "f32" (default) | "f64"
         Arithmetic of the SVI step and of the latent samples of the prediction calls.  "f32": everything above.  "f64": the
         step runs on the float64 feature matrix (rr_featmat64_glm_step_draws: features, the three products on the f64 matrix
@@ -176,7 +178,12 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
         <= 128, minibatch <= 64, D <= 32768), runs on a fixed chain of four kernels per step with many steps queued per library
         call (rr_svi_wide.hip) -- the same minibatches, draws (either sampler), updaters and likelihoods, float64 throughout,
         bitwise reproducible.  A shape the LDS kernel takes still takes it; any other child, several ranks or minibatches split
-        over ``devices=`` keep the step-per-call loop (``fused_bases`` keeps its meaning for the LDS kernel only).  The random
+        over ``devices=`` keep the step-per-call loop (``fused_bases`` keeps its meaning for the LDS kernel only, with one
+        addition: under ``fused_bases="all+gm"`` the wide loop takes FastFoodGM spectral-mixture components on Xdim <= 128 too
+        -- rr_glm_sviwgm_create: a work item owns a run of a component's frequencies with all four their columns, the 2 Xdim
+        [mean | length scales] gradients are summed per item in a fixed order -- next to random Fourier, FastFoodRBF and linear
+        children, whenever rr_glm_sviwgm_supported takes the shape; under "fourier" or "all" a FastFoodGM child routes as without
+        the keyword, and centre and polynomial children keep the step-per-call loop under every value).  The random
         starts are scored in chunks whose uploads stay within the loop's block size.  False: every fit takes the loop it always
         took.  Any other value: ValueError at ``fit``, before any device call."""
 
@@ -517,7 +524,9 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
                 tables = sum(kid.W.shape[0] * c[1].n if c[0] in ("rff", "gm") else (c[1].d * c[1].M if c[0] == "centres" else 0)
                              for kid, c in zip(kids, children))
                 if gm:
-                    if _hip.svi_supported_gm(F, self.K, self.nsamples, M, len(children), dsum, n_ls, tables):
+                    # (the tests' switch: with a spectral-mixture child, wide_fused=True sends what this kernel would take on too)
+                    forced = self._wide_fused_force and getattr(self, "wide_fused", False) is True and any(c[0] == "gm" for c in children)
+                    if not forced and _hip.svi_supported_gm(F, self.K, self.nsamples, M, len(children), dsum, n_ls, tables):
                         return _FusedLoop(self, feats, n_lik, children, y, likelihood_args, gm_children=True)
                 elif _hip.svi_supported_all(F, self.K, self.nsamples, M, len(children), dsum, n_ls, tables):
                     return _FusedLoop(self, feats, n_lik, children, y, likelihood_args, all_children=True)
@@ -529,6 +538,12 @@ class GeneralizedLinearModel(BaseEstimator, RegressorMixin):
                     and all(c[0] == "rff" or (c[0] == "linear" and c[1] <= 128) for c in children) \
                     and _hip.sviw_supported(F, self.K, self.nsamples, M, len(children), dsum, n_ls):
                 return _FusedLoop(self, feats, n_lik, children, y, likelihood_args, wide=True)
+            # ... and, under fused_bases="all+gm", spectral-mixture components among them (rr_glm_sviwgm_create)
+            gm_cols = sum(4 * c[1].n for c in children if c[0] == "gm")
+            if gm and gm_cols and getattr(self, "wide_fused", False) is True \
+                    and all(c[0] in ("rff", "gm") or (c[0] == "linear" and c[1] <= 128) for c in children) \
+                    and _hip.sviw_supported_gm(F, self.K, self.nsamples, M, len(children), dsum, n_ls, gm_cols):
+                return _FusedLoop(self, feats, n_lik, children, y, likelihood_args, wide=True, gm_children=True)
         return _ResidentLoop(self, feats, n_lik, children, comm=comm)
 
     def _reference_draws(self, out=None):

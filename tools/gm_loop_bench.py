@@ -18,7 +18,17 @@ Arms: "fused" -- the opt-in as a user would set it; "step" -- the same estimator
 and 2s this is also what the default keywords run); "host" -- default keywords, no device loop.  Every fit runs in a child
 process of its own under a time limit: a warm-up fit, then the timed one (wall time of `fit`, which ends with the read-back of
 the parameters, over maxiter).  The arms alternate, repetition by repetition; the first child that fails ends the run.  One JSON
-line per (case, sampler) at the end."""
+line per (case, sampler) at the end.
+
+  python tools/gm_loop_bench.py --wide [--shapes 1x32@10,2x32@10,...] [--steps 300] [--warmup 50] [--rounds 3] [--force] [--out FILE]
+
+The wide small-minibatch loop (``wide_fused=True`` next to the opt-in: rr_svi_wide.hip with RR_SGD_CHILD_GM items) against
+``wide_fused=False`` (what those shapes took before: the step-per-call loop above the LDS kernel's range), as
+tools/glm_wide_bench.py measures the loop's other children: shapes are <components>x<nbases>@<minibatch> on Xdim = 4, K = 10, 50
+samples, sampler="device", N = 2000; the two arms alternate in ONE process, --rounds rounds; microseconds per step from the loop's
+own clock (`_resident_clock`: (end of fit - mark after the warm-up steps) / steps, the device synchronised at each mark); the
+table gives the median and the spread (min ... max) of the rounds and the loop each arm ran.  --force sets the tests' switch, so
+that a shape the LDS kernel would take (F <= 200) is measured on the wide loop too."""
 import argparse
 import json
 import os
@@ -89,8 +99,98 @@ def one_fit(case, sampler, arm, maxiter):
     return {"arm": arm, "route": route, "F": F, "ms_per_step": 1e3 * wall / maxiter, "weights_abs_sum": check}
 
 
+def wide_fit(ncomp, nbases, batch, wide, steps, warmup, force):
+    """one fit of the --wide table: (loop that ran, microseconds per step)"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import revrand_amd.basis_functions as bs
+    from revrand_amd import _hip
+    from revrand_amd import glm as glm_mod
+    from revrand_amd import likelihoods as lk
+    from revrand_amd.btypes import Bound, Parameter, Positive
+    from revrand_amd.glm import GeneralizedLinearModel
+    d = 4
+    rs = np.random.RandomState(7)
+    X = rs.randn(GLM["N"], d)
+    y = np.sin(X[:, 0]) + 0.3 * X[:, 1] + 0.1 * rs.randn(GLM["N"])
+    basis = None
+    for i in range(ncomp):
+        b = bs.FastFoodGM(nbases=nbases, Xdim=d, random_state=10 + i, mean=Parameter(0.2 * (i % 4 + 1) * np.ones(d), Bound()),
+                          lenscale=Parameter((1.0 + 0.25 * (i % 4)) * np.ones(d), Positive()))
+        basis = b if basis is None else basis + b
+    glm = GeneralizedLinearModel(lk.Gaussian(), basis, K=GLM["K"], nsamples=GLM["L"], batch_size=batch, maxiter=steps + warmup,
+                                 nstarts=0, random_state=1, sampler="device", resident_bases="all", fused_bases="all+gm",
+                                 wide_fused=wide)
+    glm._wide_fused_force = bool(force and wide)
+    if not wide:
+        glm._fused_sgd = False     # the step-per-call loop, whatever the LDS kernel would take
+    ran = {"wide": 0, "fused": 0, "resident": 0}
+    real = (_hip.WideSvi.run, _hip.FusedSvi.run, _hip.ResidentSgd.step)
+
+    def wrun(self, n, *a, **k):
+        ran["wide"] += n
+        real[0](self, n, *a, **k)
+        self.dev.sync()
+
+    def frun(self, n, *a, **k):
+        ran["fused"] += n
+        real[1](self, n, *a, **k)
+        self.dev.sync()
+
+    def step(self, *a, **k):
+        ran["resident"] += 1
+        return real[2](self, *a, **k)
+    _hip.WideSvi.run, _hip.FusedSvi.run, _hip.ResidentSgd.step = wrun, frun, step
+    old = glm_mod._FusedLoop.BLOCK_STEPS
+    glm_mod._FusedLoop.BLOCK_STEPS = warmup
+    try:
+        np.random.seed(0)
+        glm.fit(X, y)
+    finally:
+        _hip.WideSvi.run, _hip.FusedSvi.run, _hip.ResidentSgd.step = real
+        glm_mod._FusedLoop.BLOCK_STEPS = old
+    ck = glm.__dict__["_resident_clock"]
+    loop = max(ran, key=ran.get)
+    assert ran[loop] == steps + warmup, ran
+    mark = ck[warmup] if loop == "resident" else ck[0]     # (the fused loops: the first mark closes the warm-up block)
+    return loop, int(glm.D_), 1e6 * (ck[-1] - mark) / steps
+
+
+def wide_table(a):
+    import numpy as np
+    out = open(a.out, "w") if a.out else None
+    print("%9s %6s %4s | %-9s %9s (%9s ... %9s) | %-9s %9s (%9s ... %9s) | ratio" %
+          ("shape", "F", "M", "True", "us/step", "min", "max", "False", "us/step", "min", "max"))
+    for shape in a.shapes.split(","):
+        comp, batch = shape.split("@")
+        ncomp, nbases = (int(v) for v in comp.split("x"))
+        res, loops, F = {True: [], False: []}, {}, 0
+        for _ in range(a.rounds):
+            for wide in (True, False):
+                loops[wide], F, us = wide_fit(ncomp, nbases, int(batch), wide, a.steps, a.warmup, a.force)
+                res[wide].append(us)
+        med = {w: float(np.median(res[w])) for w in res}
+        print("%9s %6d %4d | %-9s %9.1f (%9.1f ... %9.1f) | %-9s %9.1f (%9.1f ... %9.1f) | %.2f" %
+              (comp, F, int(batch), loops[True], med[True], min(res[True]), max(res[True]),
+               loops[False], med[False], min(res[False]), max(res[False]), med[False] / med[True]), flush=True)
+        if out:
+            out.write(json.dumps({"shape": shape, "F": F, "M": int(batch), "loops": {str(k): v for k, v in loops.items()},
+                                  "us_per_step": {str(k): v for k, v in res.items()}}) + "\n")
+            out.flush()
+    if out:
+        out.close()
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--wide", action="store_true", help="the wide_fused=True / False table (one process, arms alternating)")
+    ap.add_argument("--shapes", default="1x32@10,2x32@10,4x32@10,8x32@10,4x256@10,4x32@32,4x32@64")
+    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--force", action="store_true")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--cases", default="1,2,1s,2s")
     ap.add_argument("--samplers", default="device,host")
@@ -98,6 +198,8 @@ def main():
     ap.add_argument("--timeout", type=int, default=300, help="seconds per child process (one warm-up and one timed fit)")
     ap.add_argument("--child", nargs=3, metavar=("CASE", "SAMPLER", "ARM"), help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.wide:
+        return wide_table(a)
     if a.child:
         print("RESULT " + json.dumps(one_fit(a.child[0], a.child[1], a.child[2], a.maxiter)), flush=True)
         return 0
