@@ -11,6 +11,7 @@
 // Kernels: rr_rff_features_t_kernel (feature-major Phi^T + Phi m), rr_gemm_tn_f32_kernel (U = (Phi^T)^T C on the
 // SYRK kernel's LDS-DMA / MFMA structure, plain f32 stores), rr_rowdot_kernel, rr_grad_t_kernel.
 #include "rr_internal.h"
+#include "rr_svi_common.h"
 #include "rr_mfma_tile.h"
 #include "rr_syrk_args.h"  // rr_launch_syrk_f64
 #include "rr_workers.h"
@@ -1415,13 +1416,6 @@ rr_glm_grad_t_kernel(const TX *__restrict__ X, int64_t N, int64_t ldx, const flo
 // f) is a pure function of (seed, step, kl F + f), two SplitMix64 rounds + Box-Muller.
 //   E[kl][f] = e;   WSs[kl][f] = (m[f][k] + sqrt(C[f][k]) e) / (K L),  k = kl / L
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t rr_splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 __global__ void __launch_bounds__(256)
 rr_glm_draw_kernel(const double *__restrict__ mdev, const double *__restrict__ Cdev, int F, int K, int L, int64_t Fp,
                    int64_t klp, uint64_t seed, uint64_t step, const float *__restrict__ Egiven, float *__restrict__ E,
@@ -1436,10 +1430,7 @@ rr_glm_draw_kernel(const double *__restrict__ mdev, const double *__restrict__ C
             e = Egiven[(size_t)kl * F + f];
         } else {
             const uint64_t ctr = (uint64_t)kl * (uint64_t)F + (uint64_t)f;
-            const uint64_t h = rr_splitmix64(rr_splitmix64(seed ^ (step * 0xD1B54A32D192ED03ull)) ^ ctr);
-            const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);  // (0, 1]
-            const float u2 = (float)(uint32_t)((h >> 8) & 0xFFFFFFu) * (1.0f / 16777216.0f);
-            e = sqrtf(-2.0f * __logf(u1)) * __builtin_amdgcn_cosf(u2);  // cos of u2 revolutions
+            e = rr_svi_draw(rr_svi_stepkey(seed, step), ctr);
         }
         const int k = (int)(kl / L);
         w = (float)((mdev[(size_t)f * K + k] + sqrt(Cdev[(size_t)f * K + k]) * (double)e) / ((double)K * (double)L));
@@ -3457,6 +3448,7 @@ __global__ void __launch_bounds__(256) rr_glm_sgd_update_kernel(const SgdUpdArgs
     if (tid == 0) a.npart[blockIdx.x] = n2;
     if (!live) return;
     const double zz = a.z[p], lo = a.lower[p], hi = a.upper[p];
+    // (rr_svi_update's switch, on the state in HBM: through the shared form's references this kernel's code changed)
     if (zz <= lo) g = (g <= 0.0 || g != g) ? g : 0.0;  // np.minimum(grad, 0) on a coordinate sitting on its lower bound
     if (zz >= hi) g = (g >= 0.0 || g != g) ? g : 0.0;
     double zn;
@@ -3502,7 +3494,7 @@ rr_glm_sgd_finish_kernel(const double *__restrict__ x, const double *__restrict_
     for (int i = tid; i < nblocks; i += 256) acc += npart[i];
     const double n2 = rr_block_sum256(acc, sh);
     double lz = 0.0;
-    if (tid < K) {
+    if (tid < K) {   // (rr_svi_logz's formula with the result in a register: a shared form that returns it changed the kernels' code)
         double mx = -INFINITY;
         for (int j = 0; j < K; ++j) mx = fmax(mx, -0.5 * ((double)F * 1.8378770664093453 + red[j * K + tid]));
         double sm = 0.0;
@@ -3945,9 +3937,7 @@ static void sgd_update_args(rr_glm_sgd *o, const SgdStepIn &in, FmPass2 &s, SgdU
     a.bmag = in.bmag; a.nrows = (double)in.rows_total;
     a.tot = in.totals_on_device ? s.kacc + 2 * s.kcap : nullptr;
     for (int i = 0; i < 4; ++i) a.up[i] = o->up[i];
-    const double tt = (double)(o->t + 1);
-    a.b1t = 1.0 - pow(o->up[1], tt);
-    a.b2t = 1.0 - pow(o->up[2], tt);
+    rr_svi_adam_bias(o->up, o->t + 1, a.b1t, a.b2t);
 }
 
 // (dT summed over all rows:) the length scales' gradient and update -- the next step's features may start --, then

@@ -19,9 +19,9 @@
 // follows the library's convention: rr_glm_grad_t64_kernel adds its block partials atomically unless the context is
 // deterministic, exactly like rr_grad_t64_kernel).
 //
-// The likelihood formulas below (glm64_lik) are the float64 master copy for the step-per-call pipeline; rr_svi.hip's svi_lik
-// is the fused small-minibatch kernel's own copy (sharing one through a header would change that kernel's code generation, and
-// its softplus-link Poisson keeps the reference's clamp where this one is division-free).  tests/glm_f64_cases.py holds these
+// The likelihood formulas below (glm64_lik) are the float64 master copy for the step-per-call pipeline; rr_svi_lik
+// (rr_svi_common.h) is the small-minibatch loops' own (its softplus-link Poisson keeps the reference's clamp where this one is
+// division-free).  tests/glm_f64_cases.py holds these
 // to (16 + 4 |f|) 2^-53 S per element over -200 <= f <= 200.
 // =============================================================================================
 #include <algorithm>

@@ -38,6 +38,7 @@
 // rr_glm_svi_starts evaluates the random starts of structured_sgd (decorators.py:541-583) -- nstarts candidates, each on its
 // own minibatch with its own draws -- as ONE launch, one workgroup per candidate (objective only).
 #include "rr_internal.h"
+#include "rr_svi_common.h"
 
 #include <algorithm>
 
@@ -92,27 +93,6 @@ struct SviArgs {
     long long *prof;  // RR_SVI_PROF=1: workgroup 0's time per phase (100 MHz ticks), summed over the steps
 };
 
-__device__ __forceinline__ uint64_t svi_splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// the draw of rr_glm_draw_kernel (rr_elbo.hip) for (seed, step, counter)
-__device__ __forceinline__ float svi_draw(uint64_t stepkey, uint64_t ctr) {
-    const uint64_t h = svi_splitmix64(stepkey ^ ctr);
-    const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);
-    const float u2 = (float)(uint32_t)((h >> 8) & 0xFFFFFFu) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * __logf(u1)) * __builtin_amdgcn_cosf(u2);
-}
-
-__device__ __forceinline__ double svi_softplus(double f) { return fmax(f, 0.0) + log1p(exp(-fabs(f))); }
-__device__ __forceinline__ double svi_expit(double f) {
-    const double e = exp(-fabs(f));
-    return f >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
-}
-
 // per input dimension, what a child's features multiply x (or x - c) by: 1 / (2 pi l) (random Fourier), 1 / (2 l^2) (radial:
 // X and C are divided by 2 l^2 BEFORE the squared distance, basis_functions.py:685-686), 1 / l (sigmoid, :784); a
 // spectral-mixture mean multiplies x itself: mean / (2 pi), revolutions like the rest
@@ -134,33 +114,6 @@ __device__ __forceinline__ double svi_ls_grad(int kind, double sm2, double l) {
     return sm2 / (1.0 * (l * l));
 }
 
-// d loglike / d f and the f-dependent part of loglike (Gaussian: the squared error)   likelihoods.py:46-104,171-233,298-368,456-521
-__device__ __forceinline__ void svi_lik(int lik, double f, double y, double n, double ivar, double &df, double &ll) {
-    if (lik == RR_LIK_BERNOULLI) {
-        df = y - svi_expit(f);
-        ll = y * f - svi_softplus(f);
-    } else if (lik == RR_LIK_BINOMIAL) {
-        df = y - n * svi_expit(f);
-        ll = y * f - n * svi_softplus(f);
-    } else if (lik == RR_LIK_GAUSSIAN) {
-        const double er = y - f;
-        df = er * ivar;
-        ll = er * er;
-    } else if (lik == RR_LIK_POISSON_EXP) {
-        const double g = exp(f);
-        df = y - g;
-        ll = y * f - g;
-    } else {
-        const double g = fmax(svi_softplus(f), 1e-100);
-        df = svi_expit(f) * (y / g - 1.0);
-        ll = y * log(g) - g;
-    }
-}
-
-typedef __attribute__((address_space(3))) double ldsd;   // LDS pointers keep their address space: ds_read / ds_write, never flat
-typedef __attribute__((address_space(3))) float ldsf;
-typedef __attribute__((address_space(3))) unsigned char ldsb;
-
 // The workgroup barrier for data exchanged through LDS: orders LDS accesses only (s_waitcnt lgkmcnt(0) + s_barrier), so
 // global loads in flight -- the next step's minibatch rows, prefetched a step ahead -- are not waited for at every barrier
 // (__syncthreads() waits for vmcnt(0) as well: the prefetch's HBM latency then lands on whatever barrier comes next).
@@ -171,16 +124,10 @@ __device__ __forceinline__ void svi_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-__device__ __forceinline__ double svi_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // sum over the block, fixed order (the same bits in every workgroup that sums the same values); all threads get it
 __device__ __forceinline__ double svi_block_sum(double v, ldsd *red) {
     const int tid = threadIdx.x;
-    v = svi_wave_sum(v);
+    v = rr_svi_wave_sum(v);
     svi_sync();
     if ((tid & 63) == 0) red[tid >> 6] = v;
     svi_sync();
@@ -206,10 +153,6 @@ __device__ __forceinline__ void svi_wait(unsigned int *ctr, unsigned int target)
         __threadfence();
     }
     __syncthreads();   // the full barrier (global memory too): what thread 0 acquired is ordered before every wave's reads
-}
-
-__device__ __forceinline__ double svi_xval(const SviChild &c, int64_t row, int i) {
-    return c.x_f64 ? ((const double *)c.X)[row * c.ldx + i] : (double)((const float *)c.X)[row * c.ldx + i];
 }
 
 #define SVI_GREG 2  // gathered X entries a thread holds in registers between the loads and their use (M dsum <= 2 x 512)
@@ -277,7 +220,7 @@ __device__ __forceinline__ void svi_gather_issue(const SviArgs &a, const int *id
             const int r = e / a.dsum, o = e % a.dsum;
             int c = 0;
             while (c + 1 < a.nkids && o >= a.kid[c + 1].xoff) ++c;
-            g.x[u] = svi_xval(a.kid[c], (int64_t)idx[r], o - a.kid[c].xoff);
+            g.x[u] = rr_svi_xval(a.kid[c], (int64_t)idx[r], o - a.kid[c].xoff);
         }
     }
     g.y = g.n = g.lc = 0.0;
@@ -362,7 +305,7 @@ __device__ __forceinline__ void svi_features(const SviArgs &a, const SviLds &s, 
                     const double t = (s.Xb[r * a.dsum + k.xoff + i] - C[i * k.n + j]) * il[k.n_ls == 1 ? 0 : i];
                     z = fma(t, t, z);
                 }
-                s.Phi[r * a.Fp + k.col0 + j] = k.radial ? exp(-z) : svi_expit(sqrt(z));
+                s.Phi[r * a.Fp + k.col0 + j] = k.radial ? exp(-z) : rr_svi_expit(sqrt(z));
             }
         } else if (k.kind == RR_SGD_CHILD_GM) {
             // cos(a + b) | sin(a + b) | cos(a - b) | sin(a - b), each / sqrt(2 n): a = x . V[:, j] / (2 pi l), b per row (above)
@@ -412,7 +355,7 @@ __device__ __forceinline__ void svi_draws(const SviArgs &a, const SviLds &s, con
     if (E) {
         for (int o = tid; o < tot; o += SVI_THREADS) s.Ef[o] = E[o];
     } else {
-        for (int o = tid; o < tot; o += SVI_THREADS) s.Ef[o] = svi_draw(stepkey, (uint64_t)kl0 * (uint64_t)a.F + (uint64_t)o);
+        for (int o = tid; o < tot; o += SVI_THREADS) s.Ef[o] = rr_svi_draw(stepkey, (uint64_t)kl0 * (uint64_t)a.F + (uint64_t)o);
     }
 }
 
@@ -458,7 +401,7 @@ __device__ __forceinline__ void svi_pass1(const SviArgs &a, const SviLds &s, dou
             const int lo = rb * 16 + kk + 4 * v, ro = cb * 16 + i;
             if (lo < L && ro < M) {
                 double df, ll;
-                svi_lik(a.lik, acc[v], s.yb[ro], s.nb[ro], ivar, df, ll);
+                rr_svi_lik(a.lik, acc[v], s.yb[ro], s.nb[ro], ivar, df, ll);
                 s.dfs[lo * M + ro] = df;
                 ll_acc += ll;
             }
@@ -514,19 +457,6 @@ __device__ __forceinline__ void svi_pass2(const SviArgs &a, const SviLds &s) {
     }
 }
 
-// log N_jl = -(F log 2 pi + q_jl) / 2 and log z_l = logsumexp_j log N_jl from the full q (K, K) in s.q      glm.py:221-222
-__device__ __forceinline__ void svi_logz(const SviArgs &a, const SviLds &s) {
-    const int tid = threadIdx.x, K = a.K;
-    if (tid < K) {
-        double mx = -INFINITY;
-        for (int j = 0; j < K; ++j) mx = fmax(mx, -0.5 * ((double)a.F * 1.8378770664093453 + s.q[j * K + tid]));
-        double sm = 0.0;
-        for (int j = 0; j < K; ++j) sm += exp(-0.5 * ((double)a.F * 1.8378770664093453 + s.q[j * K + tid]) - mx);
-        s.logz[tid] = log(sm) + mx;
-    }
-    svi_sync();
-}
-
 // q[k][l] for every l: one wave per l (out: LDS or HBM)
 template <typename P>
 __device__ __forceinline__ void svi_qrow(const SviArgs &a, const SviLds &s, int k, P out) {
@@ -538,7 +468,7 @@ __device__ __forceinline__ void svi_qrow(const SviArgs &a, const SviLds &s, int 
             const double dm = s.xm[f * K + k] - s.xm[f * K + l];
             acc += log(dc) + dm * dm / dc;
         }
-        acc = svi_wave_sum(acc);
+        acc = rr_svi_wave_sum(acc);
         if (lane == 0) out[l] = acc;
     }
 }
@@ -550,7 +480,7 @@ __device__ __forceinline__ void svi_child_sums(const SviArgs &a, const SviLds &s
         double acc = 0.0;
         const int lo = a.kid[c].col0 * K, hi = (a.kid[c].col0 + a.kid[c].width) * K;
         for (int o = lo + lane; o < hi; o += 64) acc += s.xm[o] * s.xm[o] + s.xC[o];
-        acc = svi_wave_sum(acc);
+        acc = rr_svi_wave_sum(acc);
         if (lane == 0) s.Rc[c] = acc;
     }
 }
@@ -564,46 +494,9 @@ __device__ __forceinline__ double svi_neg_elbo(const SviArgs &a, const SviLds &s
         part += -0.5 * K * ((double)a.kid[c].width * log(reg)) - 0.5 * (s.Rc[c] / reg);
     }
     for (int k = lane; k < K; k += 64) part -= s.logz[k];
-    part = svi_wave_sum(part);
+    part = rr_svi_wave_sum(part);
     const double elbo = (ell_total * a.bmag - 0.5 * F * K * 1.8378770664093453 + part + log((double)K)) / K;
     return -elbo;
-}
-
-// one coordinate's truncation + updater + clip (sgd.py:404-420, :14-330); g is the gradient in z space
-__device__ __forceinline__ double svi_update(const SviArgs &a, double zz, double g, double lo, double hi, double &s1, double &s2,
-                                             double b1t, double b2t) {
-#pragma clang fp contract(off)
-    if (zz <= lo) g = (g <= 0.0 || g != g) ? g : 0.0;
-    if (zz >= hi) g = (g >= 0.0 || g != g) ? g : 0.0;
-    double zn;
-    switch (a.updater) {
-        case RR_UPD_SGD: zn = zz - a.up[0] * g; break;
-        case RR_UPD_ADADELTA: {
-            const double eg2 = a.up[0] * s1 + (1 - a.up[0]) * (g * g);
-            const double dx = -g * sqrt(s2 + a.up[1]) / sqrt(eg2 + a.up[1]);
-            s1 = eg2;
-            s2 = a.up[0] * s2 + (1 - a.up[0]) * (dx * dx);
-            zn = zz + dx;
-        } break;
-        case RR_UPD_ADAGRAD: {
-            const double h = s1 + g * g;
-            s1 = h;
-            zn = zz - a.up[0] * g / (a.up[1] + sqrt(h));
-        } break;
-        case RR_UPD_MOMENTUM: {
-            const double dx = a.up[0] * s1 - a.up[1] * g;
-            s1 = dx;
-            zn = zz + dx;
-        } break;
-        default: {
-            const double m = a.up[1] * s1 + (1 - a.up[1]) * g;
-            const double v = a.up[2] * s2 + (1 - a.up[2]) * (g * g);
-            s1 = m;
-            s2 = v;
-            zn = zz - a.up[0] * (m / b1t) / (sqrt(v / b2t) + a.up[3]);
-        }
-    }
-    return zn < lo ? lo : (zn > hi ? hi : zn);
 }
 
 // RR_SVI_PROF=1: workgroup 0's thread 0 accumulates the 100 MHz clock per phase in REGISTERS (a read-modify-write of HBM per
@@ -692,7 +585,7 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
     svi_load_z(a, s, k, a.z, true);
     svi_sync();
     svi_form_x(a, s, k);
-    svi_draws(a, s, a.E ? a.E + (size_t)k * L * F : nullptr, svi_splitmix64(a.seed ^ (a.key0 * 0xD1B54A32D192ED03ull)), k * L);
+    svi_draws(a, s, a.E ? a.E + (size_t)k * L * F : nullptr, rr_svi_stepkey(a.seed, a.key0), k * L);
     svi_sync();
     for (int t = 0; t < a.steps; ++t) {
         const int par = t & 1;
@@ -778,7 +671,7 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
                     acc = fma(W[j] * s.Xb[r * a.dsum + kd.xoff + i], eps * s.Phi[r * a.Fp + jc] - epc * s.Phi[r * a.Fp + js], acc);
                 }
             }
-            acc = svi_wave_sum(acc);
+            acc = rr_svi_wave_sum(acc);
             if (lane == 0) s.gls[h] = acc;
         }
         SVI_MARK(4);
@@ -787,7 +680,8 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
         for (int o = tid; o < K * K; o += SVI_THREADS) s.q[o] = a.pubrow[(size_t)par * K * K + o];
         svi_sync();
         SVI_MARK(5);
-        svi_logz(a, s);
+        rr_svi_logz(a.F, a.K, s.q, s.logz);
+        svi_sync();
         if (tid < K) {
             const double lN = -0.5 * ((double)F * 1.8378770664093453 + s.q[tid * K + k]);
             s.alpha[tid] = exp(lN - s.logz[k]) + exp(lN - s.logz[tid]);
@@ -816,7 +710,7 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
             if (s.lg[(cov ? fk : 0) + (int64_t)f * K + k]) g *= cov ? Ck : mkv;
             n2 += g * g;
             double s1 = s.s1c[p], s2 = s.s2c[p];
-            const double zn = svi_update(a, s.zc[p], g, s.loc[p], s.hic[p], s1, s2, b1t, b2t);
+            const double zn = rr_svi_update(a, s.zc[p], g, s.loc[p], s.hic[p], s1, s2, b1t, b2t);
             s.s1c[p] = s1;
             s.s2c[p] = s2;
             s.zc[p] = zn;
@@ -838,7 +732,7 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
         // ---- d (of the NEXT step, while the slowest component gets to the barrier): its draws into LDS
         if (t + 1 < a.steps)
             svi_draws(a, s, a.E ? a.E + ((size_t)(t + 1) * K * L + (size_t)k * L) * F : nullptr,
-                      svi_splitmix64(a.seed ^ ((a.key0 + (uint64_t)(t + 1)) * 0xD1B54A32D192ED03ull)), k * L);
+                      rr_svi_stepkey(a.seed, a.key0 + (uint64_t)(t + 1)), k * L);
         SVI_MARK(8);
         svi_wait(a.bar + 1, (unsigned)(t + 1) * (unsigned)K);
         SVI_MARK(9);
@@ -869,7 +763,7 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
             if (s.lg[2 * fk + p]) g *= s.xs[p];
             n2s = g * g;
             double s1 = s.s1s[p], s2 = s.s2s[p];
-            s.zs[p] = svi_update(a, s.zs[p], g, s.los[p], s.his[p], s1, s2, b1t, b2t);
+            s.zs[p] = rr_svi_update(a, s.zs[p], g, s.los[p], s.his[p], s1, s2, b1t, b2t);
             s.s1s[p] = s1;
             s.s2s[p] = s2;
         }
@@ -880,10 +774,10 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_steps_kernel(const Svi
                 tot += s.psc[j * npub + a.n_ls + 2];
                 ell += s.psc[j * npub + a.n_ls + 1] / L;
             }
-            tot = svi_wave_sum(tot) + n2s;
+            tot = rr_svi_wave_sum(tot) + n2s;
             double llc = s.misc[0];
             if (a.n_lik) llc = -0.5 * log(2.0 * 3.141592653589793 * s.xs[nk]) * (double)M;
-            ell = svi_wave_sum(ell) + llc * K;
+            ell = rr_svi_wave_sum(ell) + llc * K;
             const double obj = svi_neg_elbo(a, s, ell, lane);
             if (lane == 0) {
                 a.norms[gt] = sqrt(tot);
@@ -935,7 +829,7 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_starts_kernel(const Sv
     svi_features(a, s, gth);
     const double ivar = a.n_lik ? 1.0 / s.xs[nk] : 0.0;
     double ell = 0.0;
-    const uint64_t stepkey = svi_splitmix64(a.seed ^ ((a.key0 + (uint64_t)c) * 0xD1B54A32D192ED03ull));
+    const uint64_t stepkey = rr_svi_stepkey(a.seed, a.key0 + (uint64_t)c);
     for (int k = 0; k < K; ++k) {
         svi_sync();
         for (int f = tid; f < F; f += SVI_THREADS) {
@@ -951,7 +845,8 @@ __global__ void __launch_bounds__(SVI_THREADS) rr_glm_svi_starts_kernel(const Sv
     for (int k = 0; k < K; ++k) svi_qrow(a, s, k, s.q + k * K);
     svi_child_sums(a, s);
     svi_sync();
-    svi_logz(a, s);
+    rr_svi_logz(a.F, a.K, s.q, s.logz);
+    svi_sync();
     if (tid < 64) {
         double llc = s.misc[0];
         if (a.n_lik) llc = -0.5 * log(2.0 * 3.141592653589793 * s.xs[nk]) * (double)M;
@@ -971,12 +866,8 @@ struct rr_glm_svi {
     size_t bias_cap = 0;
     std::vector<double> hbias;
     std::vector<double *> dW;
-    unsigned char *islog = nullptr;
-    double *lower = nullptr, *upper = nullptr;
-    int64_t maxiter = 0, t = 0;
+    RrSviState st;
     size_t lds_bytes = 0;
-    double *cand = nullptr, *out = nullptr;
-    size_t cand_cap = 0;
     long long *prof = nullptr;
     int *lskind = nullptr;   // SviArgs::lskind
 };
@@ -985,8 +876,8 @@ static void svi_free(rr_glm_svi *o) {
     if (o->prof) (void)hipFree(o->prof);
     if (o->dkid) (void)hipFree(o->dkid);
     if (o->dbias) (void)hipFree(o->dbias);
-    void *q[] = {o->a.z, o->a.s1, o->a.s2, o->lower, o->upper, o->islog, o->a.pubcol, o->a.pubrow, o->a.pubsc, o->a.bar,
-                 o->a.objs, o->a.norms, o->cand, o->out, o->lskind};
+    rr_svi_state_free(o->st);
+    void *q[] = {o->a.pubcol, o->a.pubrow, o->a.pubsc, o->a.bar, o->lskind};
     for (void *v : q)
         if (v) (void)hipFree(v);
     for (double *w : o->dW)
@@ -1031,18 +922,9 @@ static int svi_create(int mode, const char *who, rr_ctx *ctx, int n_children, co
                       const int *x_dtype, const int64_t *ldx, int64_t N, const void *dy, const void *drowarg, const double *dlconst,
                       int dtype, int K, int L, int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper,
                       const unsigned char *is_log, int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_svi **out) {
-    RR_REQUIRE(ctx != nullptr && children != nullptr && dX != nullptr && x_dtype != nullptr && ldx != nullptr && dy != nullptr &&
-               z0 != nullptr && lower != nullptr && upper != nullptr && is_log != nullptr && upd_par != nullptr && out != nullptr,
-               "%s: null argument", who);
-    *out = nullptr;
-    RR_REQUIRE(n_children >= 1 && n_children <= SVI_MAXCHILD, "%s: 1 <= children <= %d", who, SVI_MAXCHILD);
-    RR_REQUIRE(K >= 1 && K <= SVI_MAXK && L >= 1 && M >= 1 && N >= 1, "%s: bad K, L, minibatch or N", who);
-    RR_REQUIRE(lik >= RR_LIK_BERNOULLI && lik <= RR_LIK_POISSON_SOFTPLUS && (lik == RR_LIK_GAUSSIAN) == (n_lik == 1),
-               "%s: likelihood %d with %d likelihood parameter(s)", who, lik, n_lik);
-    RR_REQUIRE((lik == RR_LIK_BINOMIAL) == (drowarg != nullptr), "%s: the per-row argument goes with the binomial likelihood", who);
-    RR_REQUIRE(updater >= RR_UPD_SGD && updater <= RR_UPD_ADAM, "%s: unknown updater %d", who, updater);
-    RR_REQUIRE(maxiter >= 1 && maxiter < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), "%s: bad maxiter / N", who);
-    RR_REQUIRE(dtype == RR_F32 || dtype == RR_F64, "%s: bad dtype", who);
+    const int rc = rr_svi_check_create(who, SVI_MAXCHILD, SVI_MAXK, ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dtype, K, L,
+                                       M, lik, n_lik, z0, lower, upper, is_log, updater, upd_par, maxiter, (void **)out);
+    if (rc != RR_OK) return rc;
     RR_CHECK_HIP(hipSetDevice(ctx->device));
     rr_glm_svi *o = new rr_glm_svi();
     o->ctx = ctx;
@@ -1081,11 +963,8 @@ static int svi_create(int mode, const char *who, rr_ctx *ctx, int n_children, co
             if (ok) {
                 c.d = b->d; c.n = b->n; c.n_ls = k.n_ls; c.width = (gm ? 4 : 2) * b->n; c.onescol = 0;
                 ngm += gm ? 1 : 0;
-                double *w = nullptr;
-                if (hipMalloc((void **)&w, b->W.size() * 8) != hipSuccess ||
-                    hipMemcpy(w, b->W.data(), b->W.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-                    (void)hipGetLastError();
-                    if (w) (void)hipFree(w);
+                double *w = rr_svi_upload_w(b);
+                if (!w) {
                     svi_free(o);
                     rr_set_error("%s: device allocation failed", who);
                     return RR_ERR_OOM;
@@ -1164,33 +1043,16 @@ static int svi_create(int mode, const char *who, rr_ctx *ctx, int n_children, co
         return RR_ERR_UNSUPPORTED;
     }
     o->lds_bytes = svi_lds_doubles(a) * 8;
-    o->maxiter = maxiter;
-    const size_t nb = (size_t)a.np * 8;
     const int npub = nls + 4;
-    hipError_t e = hipMalloc((void **)&a.z, nb);
+    hipError_t e = rr_svi_state_alloc(o->st, a.np, maxiter, z0, lower, upper, is_log);
     if (e == hipSuccess) e = hipMalloc((void **)&o->dkid, sizeof(o->hkid));
     if (e == hipSuccess) e = hipMemcpy(o->dkid, o->hkid, sizeof(o->hkid), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&a.s1, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&a.s2, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->lower, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->upper, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->islog, (size_t)a.np);
     if (e == hipSuccess) e = hipMalloc((void **)&a.pubcol, (size_t)2 * K * 2 * a.F * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&a.pubrow, (size_t)2 * K * K * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&a.pubsc, (size_t)2 * K * npub * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&a.bar, 64);
     if (e == hipSuccess) e = hipMalloc((void **)&o->lskind, (lskind.size() + 1) * sizeof(int));
     if (e == hipSuccess && !lskind.empty()) e = hipMemcpy(o->lskind, lskind.data(), lskind.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&a.objs, (size_t)maxiter * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&a.norms, (size_t)maxiter * 8);
-    if (e == hipSuccess) e = hipMemcpy(a.z, z0, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(o->lower, lower, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(o->upper, upper, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(o->islog, is_log, (size_t)a.np, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(a.s1, 0, nb);
-    if (e == hipSuccess) e = hipMemset(a.s2, 0, nb);
-    if (e == hipSuccess) e = hipMemset(a.objs, 0, (size_t)maxiter * 8);
-    if (e == hipSuccess) e = hipMemset(a.norms, 0, (size_t)maxiter * 8);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)rr_glm_svi_steps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)rr_glm_svi_starts_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -1200,7 +1062,9 @@ static int svi_create(int mode, const char *who, rr_ctx *ctx, int n_children, co
         rr_set_error("%s: %s", who, hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP;
     }
-    a.lower = o->lower; a.upper = o->upper; a.islog = o->islog; a.kid = o->dkid; a.lskind = o->lskind;
+    const RrSviState &st = o->st;
+    a.z = st.z; a.s1 = st.s1; a.s2 = st.s2; a.lower = st.lower; a.upper = st.upper; a.islog = st.islog; a.objs = st.objs; a.norms = st.norms;
+    a.kid = o->dkid; a.lskind = o->lskind;
     if (getenv("RR_SVI_PROF")) {
         if (hipMalloc((void **)&o->prof, 16 * sizeof(long long)) == hipSuccess) (void)hipMemset(o->prof, 0, 16 * sizeof(long long));
         a.prof = o->prof;
@@ -1236,25 +1100,18 @@ int rr_glm_svi_create_gm(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *ch
 }
 
 int rr_glm_svi_set_start(rr_glm_svi *o, const double *z0, const double *lower, const double *upper, const unsigned char *is_log) {
-    RR_REQUIRE(o != nullptr && o->t == 0, "rr_glm_svi_set_start: before the first step only");
-    RR_CHECK_HIP(hipSetDevice(o->ctx->device));
-    RR_CHECK_HIP(hipStreamSynchronize(o->ctx->stream));
-    const size_t nb = (size_t)o->a.np * 8;
-    if (z0) RR_CHECK_HIP(hipMemcpy(o->a.z, z0, nb, hipMemcpyHostToDevice));
-    if (lower) RR_CHECK_HIP(hipMemcpy(o->lower, lower, nb, hipMemcpyHostToDevice));
-    if (upper) RR_CHECK_HIP(hipMemcpy(o->upper, upper, nb, hipMemcpyHostToDevice));
-    if (is_log) RR_CHECK_HIP(hipMemcpy(o->islog, is_log, (size_t)o->a.np, hipMemcpyHostToDevice));
-    return RR_OK;
+    RR_REQUIRE(o != nullptr && o->st.t == 0, "rr_glm_svi_set_start: before the first step only");
+    return rr_svi_state_set_start(o->st, o->ctx, z0, lower, upper, is_log);
 }
 
 int rr_glm_svi_run(rr_glm_svi *o, int64_t steps, const int *d_idx, const float *dE, uint64_t seed, uint64_t key0) {
     RR_REQUIRE(o != nullptr && d_idx != nullptr && steps >= 1 && steps <= (1 << 20), "rr_glm_svi_run: 1 <= steps <= 2^20 per launch");
-    RR_REQUIRE(o->t + steps <= o->maxiter, "rr_glm_svi_run: %lld steps done, %lld more asked, %lld at most", (long long)o->t,
-               (long long)steps, (long long)o->maxiter);
+    RR_REQUIRE(o->st.t + steps <= o->st.maxiter, "rr_glm_svi_run: %lld steps done, %lld more asked, %lld at most", (long long)o->st.t,
+               (long long)steps, (long long)o->st.maxiter);
     rr_ctx *c = o->ctx;
     RR_CHECK_HIP(hipSetDevice(c->device));
     SviArgs a = o->a;
-    a.idx = d_idx; a.E = dE; a.seed = seed; a.key0 = key0; a.t0 = o->t; a.steps = (int)steps;
+    a.idx = d_idx; a.E = dE; a.seed = seed; a.key0 = key0; a.t0 = o->st.t; a.steps = (int)steps;
     if (o->bias_cap < (size_t)steps) {
         RR_CHECK_HIP(hipStreamSynchronize(c->stream));
         if (o->dbias) (void)hipFree(o->dbias);
@@ -1265,17 +1122,13 @@ int rr_glm_svi_run(rr_glm_svi *o, int64_t steps, const int *d_idx, const float *
     }
     RR_CHECK_HIP(hipStreamSynchronize(c->stream));  // (the previous launch reads dbias; hbias is reused)
     o->hbias.resize((size_t)steps * 2);
-    for (int64_t t = 0; t < steps; ++t) {
-        const double tt = (double)(o->t + t + 1);
-        o->hbias[(size_t)2 * t] = 1.0 - pow(a.up[1], tt);
-        o->hbias[(size_t)2 * t + 1] = 1.0 - pow(a.up[2], tt);
-    }
+    for (int64_t t = 0; t < steps; ++t) rr_svi_adam_bias(a.up, o->st.t + t + 1, o->hbias[(size_t)2 * t], o->hbias[(size_t)2 * t + 1]);
     RR_CHECK_HIP(hipMemcpyAsync(o->dbias, o->hbias.data(), (size_t)steps * 16, hipMemcpyHostToDevice, c->stream));
     a.bias = o->dbias;
     RR_CHECK_HIP(hipMemsetAsync(a.bar, 0, 64, c->stream));
     hipLaunchKernelGGL(rr_glm_svi_steps_kernel, dim3((unsigned)a.K), dim3(SVI_THREADS), o->lds_bytes, c->stream, a);
     RR_CHECK_HIP(hipGetLastError());
-    o->t += steps;
+    o->st.t += steps;
     return RR_OK;
 }
 
@@ -1286,43 +1139,26 @@ int rr_glm_svi_starts(rr_glm_svi *o, int ncand, const int *d_idx, const double *
     rr_ctx *c = o->ctx;
     RR_CHECK_HIP(hipSetDevice(c->device));
     SviArgs a = o->a;
-    const size_t want = (size_t)ncand * a.np;
-    if (o->cand_cap < want) {
-        RR_CHECK_HIP(hipStreamSynchronize(c->stream));
-        if (o->cand) (void)hipFree(o->cand);
-        if (o->out) (void)hipFree(o->out);
-        o->cand = o->out = nullptr;
-        o->cand_cap = 0;
-        RR_CHECK_HIP(hipMalloc((void **)&o->cand, want * 8));
-        RR_CHECK_HIP(hipMalloc((void **)&o->out, (size_t)ncand * 8));
-        o->cand_cap = want;
-    }
-    RR_CHECK_HIP(hipMemcpyAsync(o->cand, cand_host, want * 8, hipMemcpyHostToDevice, c->stream));
-    a.idx = d_idx; a.E = dE; a.seed = seed; a.key0 = key0; a.cand = o->cand; a.out = o->out;
+    const int rc = rr_svi_state_candidates(o->st, c, ncand, cand_host);
+    if (rc != RR_OK) return rc;
+    a.idx = d_idx; a.E = dE; a.seed = seed; a.key0 = key0; a.cand = o->st.cand; a.out = o->st.out;
     hipLaunchKernelGGL(rr_glm_svi_starts_kernel, dim3((unsigned)ncand), dim3(SVI_THREADS), o->lds_bytes, c->stream, a);
     RR_CHECK_HIP(hipGetLastError());
-    RR_CHECK_HIP(hipMemcpyAsync(objs_host, o->out, (size_t)ncand * 8, hipMemcpyDeviceToHost, c->stream));
+    RR_CHECK_HIP(hipMemcpyAsync(objs_host, o->st.out, (size_t)ncand * 8, hipMemcpyDeviceToHost, c->stream));
     RR_CHECK_HIP(hipStreamSynchronize(c->stream));
     return RR_OK;
 }
 
 int rr_glm_svi_read(rr_glm_svi *o, double *z, double *objs, double *norms, int64_t *steps) {
     RR_REQUIRE(o != nullptr, "rr_glm_svi_read: null argument");
-    rr_ctx *c = o->ctx;
-    RR_CHECK_HIP(hipSetDevice(c->device));
-    RR_CHECK_HIP(hipStreamSynchronize(c->stream));
-    if (z) RR_CHECK_HIP(hipMemcpy(z, o->a.z, (size_t)o->a.np * 8, hipMemcpyDeviceToHost));
-    if (objs && o->t) RR_CHECK_HIP(hipMemcpy(objs, o->a.objs, (size_t)o->t * 8, hipMemcpyDeviceToHost));
-    if (norms && o->t) RR_CHECK_HIP(hipMemcpy(norms, o->a.norms, (size_t)o->t * 8, hipMemcpyDeviceToHost));
-    if (steps) *steps = o->t;
-    if (o->prof && o->t) {
+    const int rc = rr_svi_state_read(o->st, o->ctx, z, objs, norms, steps);
+    if (rc != RR_OK) return rc;
+    if (o->prof && o->st.t) {
         long long h[16];
         RR_CHECK_HIP(hipMemcpy(h, o->prof, sizeof h, hipMemcpyDeviceToHost));
-        static const char *nm[] = {"i(prev)+loop", "a x=from_log", "b qrow+arrive", "c features", "d draws", "e pass1", "f pass2", "g wait B1", "g read q", "g logz/alpha", "h update", "B2"};
-        fprintf(stderr, "rr_glm_svi phases (workgroup 0, us per step over %lld steps):", (long long)o->t);
+        fprintf(stderr, "rr_glm_svi phases (workgroup 0, us per step over %lld steps):", (long long)o->st.t);
         const char *names[] = {"a(form x)", "b(q row)", "c(features)", "e(pass1)", "f(pass2)", "g(wait B1)", "g(logz)", "h(update)", "publish+draws", "wait B2", "i(shared)"};
-        (void)nm;
-        for (int i = 0; i < 11; ++i) fprintf(stderr, " %s=%.2f", names[i], 0.01 * (double)h[i] / (double)o->t);
+        for (int i = 0; i < 11; ++i) fprintf(stderr, " %s=%.2f", names[i], 0.01 * (double)h[i] / (double)o->st.t);
         fprintf(stderr, "\n");
     }
     return RR_OK;

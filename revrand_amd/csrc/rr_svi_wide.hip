@@ -10,9 +10,9 @@
 // the partials in item order": no floating-point atomics, the same bits every run and for every cut of a fit into calls.
 //
 //   A  grid (items, K)   mk, sk of the item's columns; the minibatch rows gathered by index; Phi of the item (component 0's
-//                        workgroup stores it for C); the draws of component k (the caller's or svi_draw's); the item's partial
+//                        workgroup stores it for C); the draws of component k (the caller's or rr_svi_draw's); the item's partial
 //                        of fs[k, l, r] = ws Phi^T; its partial of row k of the mixture's cross terms q and of sum (m^2 + C)
-//   B  grid (blocks, K)  fs = the partials in item order; dfs and the log-likelihood sums per block (svi_lik's formulas);
+//   B  grid (blocks, K)  fs = the partials in item order; dfs and the log-likelihood sums per block (rr_svi_lik's formulas);
 //                        block 0 of component k: q[k][.] and sum (m^2 + C) per child in item order
 //   C  grid (items, K)   log N, log z, alpha from q; D_r = sum_l dfs, Q = dfs^T e of the item; Edm, EdC; the gradient of the
 //                        item's 2 w coordinates of component k, log trick, |g|^2 partial, bounds, updater, clip; the item's
@@ -25,6 +25,7 @@
 // (objective only) per candidate, the candidate's x in place of x[t & 1].
 // Everything is float64 (the draws are float32 values); no lgamma, no pow: dlconst and Adam's bias come from the host.
 #include "rr_internal.h"
+#include "rr_svi_common.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -78,65 +79,10 @@ struct SwArgs {
     uint64_t stepkey;
 };
 
-// ---- the same device functions as rr_svi.hip (its kernel's own copies stay where they are: sharing them through a header
-// would change that kernel's code generation) ---------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t sw_splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// the draw of rr_glm_draw_kernel (rr_elbo.hip) for (seed, step, counter): svi_draw
-__device__ __forceinline__ float sw_draw(uint64_t stepkey, uint64_t ctr) {
-    const uint64_t h = sw_splitmix64(stepkey ^ ctr);
-    const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777216.0f);
-    const float u2 = (float)(uint32_t)((h >> 8) & 0xFFFFFFu) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * __logf(u1)) * __builtin_amdgcn_cosf(u2);
-}
-
-__device__ __forceinline__ double sw_softplus(double f) { return fmax(f, 0.0) + log1p(exp(-fabs(f))); }
-__device__ __forceinline__ double sw_expit(double f) {
-    const double e = exp(-fabs(f));
-    return f >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
-}
-
-// svi_lik: d loglike / d f and the f-dependent part of loglike (Gaussian: the squared error)
-__device__ __forceinline__ void sw_lik(int lik, double f, double y, double n, double ivar, double &df, double &ll) {
-    if (lik == RR_LIK_BERNOULLI) {
-        df = y - sw_expit(f);
-        ll = y * f - sw_softplus(f);
-    } else if (lik == RR_LIK_BINOMIAL) {
-        df = y - n * sw_expit(f);
-        ll = y * f - n * sw_softplus(f);
-    } else if (lik == RR_LIK_GAUSSIAN) {
-        const double er = y - f;
-        df = er * ivar;
-        ll = er * er;
-    } else if (lik == RR_LIK_POISSON_EXP) {
-        const double g = exp(f);
-        df = y - g;
-        ll = y * f - g;
-    } else {
-        const double g = fmax(sw_softplus(f), 1e-100);
-        df = sw_expit(f) * (y / g - 1.0);
-        ll = y * log(g) - g;
-    }
-}
-
-typedef __attribute__((address_space(3))) double ldsd;
-typedef __attribute__((address_space(3))) float ldsf;
-
-__device__ __forceinline__ double sw_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // sum over the block in a fixed order; every thread gets it (red: SW_WAVES doubles of LDS)
 __device__ __forceinline__ double sw_block_sum(double v, ldsd *red) {
     const int tid = threadIdx.x;
-    v = sw_wave_sum(v);
+    v = rr_svi_wave_sum(v);
     __syncthreads();
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
@@ -144,46 +90,6 @@ __device__ __forceinline__ double sw_block_sum(double v, ldsd *red) {
 #pragma unroll
     for (int w = 0; w < SW_WAVES; ++w) r += red[w];
     return r;
-}
-
-__device__ __forceinline__ double sw_xval(const SwChild &c, int64_t row, int i) {
-    return c.x_f64 ? ((const double *)c.X)[row * c.ldx + i] : (double)((const float *)c.X)[row * c.ldx + i];
-}
-
-// svi_update: one coordinate's truncation + updater + clip (sgd.py:404-420, :14-330); g is the gradient in z space
-__device__ __forceinline__ double sw_update(const SwArgs &a, double zz, double g, double lo, double hi, double &s1, double &s2) {
-#pragma clang fp contract(off)
-    if (zz <= lo) g = (g <= 0.0 || g != g) ? g : 0.0;
-    if (zz >= hi) g = (g >= 0.0 || g != g) ? g : 0.0;
-    double zn;
-    switch (a.updater) {
-        case RR_UPD_SGD: zn = zz - a.up[0] * g; break;
-        case RR_UPD_ADADELTA: {
-            const double eg2 = a.up[0] * s1 + (1 - a.up[0]) * (g * g);
-            const double dx = -g * sqrt(s2 + a.up[1]) / sqrt(eg2 + a.up[1]);
-            s1 = eg2;
-            s2 = a.up[0] * s2 + (1 - a.up[0]) * (dx * dx);
-            zn = zz + dx;
-        } break;
-        case RR_UPD_ADAGRAD: {
-            const double h = s1 + g * g;
-            s1 = h;
-            zn = zz - a.up[0] * g / (a.up[1] + sqrt(h));
-        } break;
-        case RR_UPD_MOMENTUM: {
-            const double dx = a.up[0] * s1 - a.up[1] * g;
-            s1 = dx;
-            zn = zz + dx;
-        } break;
-        default: {
-            const double m = a.up[1] * s1 + (1 - a.up[1]) * g;
-            const double v = a.up[2] * s2 + (1 - a.up[2]) * (g * g);
-            s1 = m;
-            s2 = v;
-            zn = zz - a.up[0] * (m / a.b1t) / (sqrt(v / a.b2t) + a.up[3]);
-        }
-    }
-    return zn < lo ? lo : (zn > hi ? hi : zn);
 }
 
 // ---- what one item holds in LDS (doubles) in kernel A (stage 0) and kernel C (stage 1) -----------------------------------------
@@ -255,7 +161,7 @@ __device__ __forceinline__ void sw_draws(const SwArgs &a, const SwChild &c, cons
         const int l = o / w, col = sw_col<GM>(c, it, o % w);
         RR_DEV_ASSERT(col >= c.col0 && col < c.col0 + c.width);
         const uint64_t ctr = ((uint64_t)k * (uint64_t)L + (uint64_t)l) * (uint64_t)F + (uint64_t)col;
-        Ef[o] = a.E ? a.E[ctr] : sw_draw(a.stepkey, ctr);
+        Ef[o] = a.E ? a.E[ctr] : rr_svi_draw(a.stepkey, ctr);
     }
 }
 
@@ -265,7 +171,7 @@ __device__ __forceinline__ void sw_gather(const SwArgs &a, const SwChild &c, lds
         const int r = e / c.d, i = e % c.d;
         const int64_t row = a.idx[r];
         RR_DEV_ASSERT(row >= 0 && row < a.N);
-        Xb[e] = sw_xval(c, row, i);
+        Xb[e] = rr_svi_xval(c, row, i);
     }
 }
 
@@ -356,7 +262,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_a_kernel(const SwArgs 
             const int r = e / w, j = e % w;
             const int64_t row = a.idx[r];
             RR_DEV_ASSERT(row >= 0 && row < a.N);
-            Phi[r * wp + j] = (c.onescol && j == 0) ? 1.0 : sw_xval(c, row, j - c.onescol);
+            Phi[r * wp + j] = (c.onescol && j == 0) ? 1.0 : rr_svi_xval(c, row, j - c.onescol);
         }
     }
     __syncthreads();
@@ -379,13 +285,13 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_a_kernel(const SwArgs 
             const double dm = xm[col * K + k] - xm[col * K + l];
             acc += log(dc) + dm * dm / dc;
         }
-        acc = sw_wave_sum(acc);
+        acc = rr_svi_wave_sum(acc);
         if (lane == 0) a.qp[((size_t)ii * K + k) * K + l] = acc;
     }
     if (wave == 0) {   // and of sum (m^2 + C) over the child's rows of component k
         double acc = 0.0;
         for (int cc = lane; cc < w; cc += 64) acc += mk[cc] * mk[cc] + sk[cc] * sk[cc];
-        acc = sw_wave_sum(acc);
+        acc = rr_svi_wave_sum(acc);
         if (lane == 0) a.Rp[(size_t)ii * K + k] = acc;
     }
 }
@@ -411,7 +317,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_b_kernel(const SwArgs 
         double n = 0.0;
         if (a.rowarg) n = a.y_f64 ? ((const double *)a.rowarg)[row] : (double)((const float *)a.rowarg)[row];
         double df;
-        sw_lik(a.lik, fs, y, n, ivar, df, ll);
+        rr_svi_lik(a.lik, fs, y, n, ivar, df, ll);
         a.dfs[(size_t)k * LM + o] = df;
     }
     ll = sw_block_sum(ll, red);
@@ -429,19 +335,6 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_b_kernel(const SwArgs 
             a.Rk[(tid - K) * K + k] = R;
         }
     }
-}
-
-// log z_l = logsumexp_j log N_jl, log N_jl = -(F log 2 pi + q_jl) / 2, from the full q in LDS   glm.py:221-222
-__device__ __forceinline__ void sw_logz(const SwArgs &a, const ldsd *q, ldsd *logz) {
-    const int tid = threadIdx.x, K = a.K;
-    if (tid < K) {
-        double mx = -INFINITY;
-        for (int j = 0; j < K; ++j) mx = fmax(mx, -0.5 * ((double)a.F * 1.8378770664093453 + q[j * K + tid]));
-        double sm = 0.0;
-        for (int j = 0; j < K; ++j) sm += exp(-0.5 * ((double)a.F * 1.8378770664093453 + q[j * K + tid]) - mx);
-        logz[tid] = log(sm) + mx;
-    }
-    __syncthreads();
 }
 
 // ---- C ------------------------------------------------------------------------------------------------------------------
@@ -479,7 +372,8 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs 
         sw_draws<GM>(a, c, it, k, w, Ef);
     }
     __syncthreads();
-    sw_logz(a, q, logz);
+    rr_svi_logz(a.F, a.K, q, logz);
+    __syncthreads();
     if (tid < K) {
         const double lN = -0.5 * ((double)F * 1.8378770664093453 + q[tid * K + k]);
         alpha[tid] = exp(lN - logz[k]) + exp(lN - logz[tid]);
@@ -520,7 +414,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs 
                 double t = 0.0;
                 for (int r = 0; r < M; ++r) t = fma(dfs[l * M + r], Phi[r * wp + cc], t);
                 const uint64_t ctr = ((uint64_t)k * (uint64_t)L + (uint64_t)l) * (uint64_t)F + (uint64_t)col;
-                ed = fma((double)(a.E ? a.E[ctr] : sw_draw(a.stepkey, ctr)), t, ed);
+                ed = fma((double)(a.E ? a.E[ctr] : rr_svi_draw(a.stepkey, ctr)), t, ed);
             }
             ed = ed / (L * sk[cc]);
         }
@@ -541,7 +435,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs 
         if (lg) g *= cov ? Ck : mkv;
         n2 += g * g;
         double s1 = a.s1[gi], s2 = a.s2[gi];
-        const double zn = sw_update(a, a.z[gi], g, a.lower[gi], a.upper[gi], s1, s2);
+        const double zn = rr_svi_update(a, a.z[gi], g, a.lower[gi], a.upper[gi], s1, s2, a.b1t, a.b2t);
         a.s1[gi] = s1;
         a.s2[gi] = s2;
         a.z[gi] = zn;
@@ -573,7 +467,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs 
                 if (mean) acc = fma(Xb[r * c.d + i], Tm[o] - Tp[o], acc);
                 else acc = fma(Wl[i * cnt + j] * Xb[r * c.d + i], Tp[o] + Tm[o], acc);
             }
-            acc = sw_wave_sum(acc);
+            acc = rr_svi_wave_sum(acc);
             if (lane == 0) a.glsp[((size_t)ii * K + k) * a.maxls + h] = acc;
         }
         return;
@@ -596,7 +490,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_c_kernel(const SwArgs 
             const int r = o / cnt, j = o % cnt;
             acc = fma(Wl[i * cnt + j] * Xb[r * c.d + i], T[o], acc);
         }
-        acc = sw_wave_sum(acc);
+        acc = rr_svi_wave_sum(acc);
         if (lane == 0) a.glsp[((size_t)ii * K + k) * a.maxls + i] = acc;
     }
 }
@@ -622,7 +516,8 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_d_kernel(const SwArgs 
         Rc[tid - 64] = acc;
     }
     __syncthreads();
-    sw_logz(a, q, logz);
+    rr_svi_logz(a.F, a.K, q, logz);
+    __syncthreads();
     // the batch's f-independent part of loglike per latent sample (the log-factorial terms)
     double lc = 0.0;
     if (tid < M && a.lconst) {
@@ -644,7 +539,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_d_kernel(const SwArgs 
             double acc = 0.0;
             for (int e = lane; e < K * c.nitems; e += 64)
                 acc += a.glsp[((size_t)(c.item0 + e % c.nitems) * K + e / c.nitems) * a.maxls + i];
-            acc = sw_wave_sum(acc);
+            acc = rr_svi_wave_sum(acc);
             if (lane == 0) gls[h] = acc;
         }
         for (int e = tid; e < a.nitems * K; e += SW_THREADS) n2 += a.n2p[e];
@@ -679,7 +574,7 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_d_kernel(const SwArgs 
             if (lg) g *= xs[p];
             n2s += g * g;
             double s1 = a.s1[gi], s2 = a.s2[gi];
-            const double zn = sw_update(a, a.z[gi], g, a.lower[gi], a.upper[gi], s1, s2);
+            const double zn = rr_svi_update(a, a.z[gi], g, a.lower[gi], a.upper[gi], s1, s2, a.b1t, a.b2t);
             a.s1[gi] = s1;
             a.s2[gi] = s2;
             a.z[gi] = zn;
@@ -693,13 +588,13 @@ __global__ void __launch_bounds__(SW_THREADS) rr_glm_sviw_d_kernel(const SwArgs 
         for (int j = lane; j < K; j += 64) ell += (a.n_lik ? -0.5 * llk[j] * ivar : llk[j]) / L;
         double llc = lc;
         if (a.n_lik) llc = -0.5 * log(2.0 * 3.141592653589793 * xs[nk]) * (double)M;
-        ell = sw_wave_sum(ell) + llc * K;
+        ell = rr_svi_wave_sum(ell) + llc * K;
         for (int ci = lane; ci < nk; ci += 64) {
             const double reg = xs[ci];
             part += -0.5 * K * ((double)a.kid[ci].width * log(reg)) - 0.5 * (Rc[ci] / reg);
         }
         for (int j = lane; j < K; j += 64) part -= logz[j];
-        part = sw_wave_sum(part);
+        part = rr_svi_wave_sum(part);
         const double elbo = (ell * a.bmag - 0.5 * F * K * 1.8378770664093453 + part + log((double)K)) / K;
         if (lane == 0) {
             *a.obj = -elbo;
@@ -776,18 +671,16 @@ struct rr_glm_sviw {
     SwChild *dkid = nullptr;
     SwItem *ditems = nullptr;
     std::vector<double *> dW;
-    unsigned char *islog = nullptr;
-    double *lower = nullptr, *upper = nullptr, *xbuf[2] = {nullptr, nullptr}, *objs = nullptr, *norms = nullptr;
-    int64_t maxiter = 0, t = 0;
+    RrSviState st;
+    double *xbuf[2] = {nullptr, nullptr};
     size_t lds_bytes = 0;
     bool gm = false;   // a spectral-mixture child among them: the kernels' <true> instances
-    double *cand = nullptr, *out = nullptr;
-    size_t cand_cap = 0, out_cap = 0;
 };
 
 static void sw_free(rr_glm_sviw *o) {
-    void *q[] = {o->dkid, o->ditems, o->a.z, o->a.s1, o->a.s2, o->lower, o->upper, o->islog, o->xbuf[0], o->xbuf[1], o->objs, o->norms,
-                 o->a.Phi, o->a.fsp, o->a.qp, o->a.Rp, o->a.dfs, o->a.llp, o->a.qf, o->a.Rk, o->a.n2p, o->a.glsp, o->cand, o->out};
+    rr_svi_state_free(o->st);
+    void *q[] = {o->dkid, o->ditems, o->xbuf[0], o->xbuf[1], o->a.Phi, o->a.fsp, o->a.qp, o->a.Rp, o->a.dfs, o->a.llp, o->a.qf, o->a.Rk,
+                 o->a.n2p, o->a.glsp};
     for (void *v : q)
         if (v) (void)hipFree(v);
     for (double *w : o->dW)
@@ -798,7 +691,7 @@ static void sw_free(rr_glm_sviw *o) {
 static void sw_form_x(rr_glm_sviw *o) {
     const int64_t np = o->a.np;
     hipLaunchKernelGGL(rr_glm_sviw_x_kernel, dim3((unsigned)((np + SW_THREADS - 1) / SW_THREADS)), dim3(SW_THREADS), 0, o->ctx->stream,
-                       (const double *)o->a.z, (const unsigned char *)o->islog, o->xbuf[o->t & 1], np);
+                       (const double *)o->st.z, (const unsigned char *)o->st.islog, o->xbuf[o->st.t & 1], np);
 }
 
 extern "C" {
@@ -892,18 +785,9 @@ static int sw_create(bool gmok, rr_ctx *ctx, int n_children, const rr_glm_sgd_ch
                      int M, int lik, int n_lik, const double *z0, const double *lower, const double *upper, const unsigned char *is_log,
                      int updater, const double *upd_par, int64_t maxiter, double bmag, rr_glm_sviw **out) {
     const char *who = gmok ? "rr_glm_sviwgm_create" : "rr_glm_sviw_create";
-    RR_REQUIRE(ctx != nullptr && children != nullptr && dX != nullptr && x_dtype != nullptr && ldx != nullptr && dy != nullptr &&
-               z0 != nullptr && lower != nullptr && upper != nullptr && is_log != nullptr && upd_par != nullptr && out != nullptr,
-               "%s: null argument", who);
-    *out = nullptr;
-    RR_REQUIRE(n_children >= 1 && n_children <= SW_MAXCHILD, "%s: 1 <= children <= %d", who, SW_MAXCHILD);
-    RR_REQUIRE(K >= 1 && K <= SW_MAXK && L >= 1 && M >= 1 && N >= 1, "%s: bad K, L, minibatch or N", who);
-    RR_REQUIRE(lik >= RR_LIK_BERNOULLI && lik <= RR_LIK_POISSON_SOFTPLUS && (lik == RR_LIK_GAUSSIAN) == (n_lik == 1),
-               "%s: likelihood %d with %d likelihood parameter(s)", who, lik, n_lik);
-    RR_REQUIRE((lik == RR_LIK_BINOMIAL) == (drowarg != nullptr), "%s: the per-row argument goes with the binomial likelihood", who);
-    RR_REQUIRE(updater >= RR_UPD_SGD && updater <= RR_UPD_ADAM, "%s: unknown updater %d", who, updater);
-    RR_REQUIRE(maxiter >= 1 && maxiter < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), "%s: bad maxiter / N", who);
-    RR_REQUIRE(dtype == RR_F32 || dtype == RR_F64, "%s: bad dtype", who);
+    const int rc = rr_svi_check_create(who, SW_MAXCHILD, SW_MAXK, ctx, n_children, children, dX, x_dtype, ldx, N, dy, drowarg, dtype, K, L,
+                                       M, lik, n_lik, z0, lower, upper, is_log, updater, upd_par, maxiter, (void **)out);
+    if (rc != RR_OK) return rc;
     for (int s = 0; s < n_children; ++s) {
         if (gmok)
             RR_REQUIRE(children[s].kind == RR_SGD_CHILD_RFF || children[s].kind == RR_SGD_CHILD_LINEAR || children[s].kind == RR_SGD_CHILD_GM,
@@ -950,11 +834,8 @@ static int sw_create(bool gmok, rr_ctx *ctx, int n_children, const rr_glm_sgd_ch
             if (ok) {
                 c.d = b->d; c.n = b->n; c.n_ls = k.n_ls; c.width = (gm ? 4 : 2) * b->n; c.onescol = 0;
                 gm_cols += gm ? c.width : 0;
-                double *w = nullptr;
-                if (hipMalloc((void **)&w, b->W.size() * 8) != hipSuccess ||
-                    hipMemcpy(w, b->W.data(), b->W.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-                    (void)hipGetLastError();
-                    if (w) (void)hipFree(w);
+                double *w = rr_svi_upload_w(b);
+                if (!w) {
                     sw_free(o);
                     rr_set_error("%s: device allocation failed", who);
                     return RR_ERR_OOM;
@@ -1011,18 +892,12 @@ static int sw_create(bool gmok, rr_ctx *ctx, int n_children, const rr_glm_sgd_ch
     a.nitems = ni;
     o->gm = gm_cols > 0;
     o->lds_bytes = (size_t)info[2];
-    o->maxiter = maxiter;
     const size_t nb = (size_t)a.np * 8, nik = (size_t)ni * K;
-    hipError_t e = hipMalloc((void **)&a.z, nb);
+    hipError_t e = rr_svi_state_alloc(o->st, a.np, maxiter, z0, lower, upper, is_log);
     if (e == hipSuccess) e = hipMalloc((void **)&o->dkid, sizeof(o->hkid));
     if (e == hipSuccess) e = hipMemcpy(o->dkid, o->hkid, sizeof(o->hkid), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc((void **)&o->ditems, (size_t)ni * sizeof(SwItem));
     if (e == hipSuccess) e = hipMemcpy(o->ditems, hitems.data(), (size_t)ni * sizeof(SwItem), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&a.s1, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&a.s2, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->lower, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->upper, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->islog, (size_t)a.np);
     if (e == hipSuccess) e = hipMalloc((void **)&o->xbuf[0], nb);
     if (e == hipSuccess) e = hipMalloc((void **)&o->xbuf[1], nb);
     if (e == hipSuccess) e = hipMalloc((void **)&a.Phi, (size_t)M * a.F * 8);
@@ -1035,17 +910,7 @@ static int sw_create(bool gmok, rr_ctx *ctx, int n_children, const rr_glm_sgd_ch
     if (e == hipSuccess) e = hipMalloc((void **)&a.Rk, (size_t)n_children * K * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&a.n2p, nik * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&a.glsp, nik * maxls * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->objs, (size_t)maxiter * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&o->norms, (size_t)maxiter * 8);
-    if (e == hipSuccess) e = hipMemcpy(a.z, z0, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(o->lower, lower, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(o->upper, upper, nb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(o->islog, is_log, (size_t)a.np, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(a.s1, 0, nb);
-    if (e == hipSuccess) e = hipMemset(a.s2, 0, nb);
     if (e == hipSuccess) e = hipMemset(a.glsp, 0, nik * maxls * 8);
-    if (e == hipSuccess) e = hipMemset(o->objs, 0, (size_t)maxiter * 8);
-    if (e == hipSuccess) e = hipMemset(o->norms, 0, (size_t)maxiter * 8);
     const void *dyn[2] = {o->gm ? (const void *)rr_glm_sviw_a_kernel<true> : (const void *)rr_glm_sviw_a_kernel<false>,
                           o->gm ? (const void *)rr_glm_sviw_c_kernel<true> : (const void *)rr_glm_sviw_c_kernel<false>};
     if (e == hipSuccess) e = hipFuncSetAttribute(dyn[0], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1057,7 +922,8 @@ static int sw_create(bool gmok, rr_ctx *ctx, int n_children, const rr_glm_sgd_ch
         rr_set_error("%s: %s", who, hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? RR_ERR_OOM : RR_ERR_HIP;
     }
-    a.lower = o->lower; a.upper = o->upper; a.islog = o->islog; a.kid = o->dkid; a.items = o->ditems;
+    const RrSviState &st = o->st;
+    a.z = st.z; a.s1 = st.s1; a.s2 = st.s2; a.lower = st.lower; a.upper = st.upper; a.islog = st.islog; a.kid = o->dkid; a.items = o->ditems;
     sw_form_x(o);
     e = hipGetLastError();
     if (e != hipSuccess) {
@@ -1087,14 +953,9 @@ int rr_glm_sviwgm_create(rr_ctx *ctx, int n_children, const rr_glm_sgd_child *ch
 }
 
 int rr_glm_sviw_set_start(rr_glm_sviw *o, const double *z0, const double *lower, const double *upper, const unsigned char *is_log) {
-    RR_REQUIRE(o != nullptr && o->t == 0, "rr_glm_sviw_set_start: before the first step only");
-    RR_CHECK_HIP(hipSetDevice(o->ctx->device));
-    RR_CHECK_HIP(hipStreamSynchronize(o->ctx->stream));
-    const size_t nb = (size_t)o->a.np * 8;
-    if (z0) RR_CHECK_HIP(hipMemcpy(o->a.z, z0, nb, hipMemcpyHostToDevice));
-    if (lower) RR_CHECK_HIP(hipMemcpy(o->lower, lower, nb, hipMemcpyHostToDevice));
-    if (upper) RR_CHECK_HIP(hipMemcpy(o->upper, upper, nb, hipMemcpyHostToDevice));
-    if (is_log) RR_CHECK_HIP(hipMemcpy(o->islog, is_log, (size_t)o->a.np, hipMemcpyHostToDevice));
+    RR_REQUIRE(o != nullptr && o->st.t == 0, "rr_glm_sviw_set_start: before the first step only");
+    const int rc = rr_svi_state_set_start(o->st, o->ctx, z0, lower, upper, is_log);
+    if (rc != RR_OK) return rc;
     sw_form_x(o);
     RR_CHECK_HIP(hipGetLastError());
     return RR_OK;
@@ -1102,27 +963,23 @@ int rr_glm_sviw_set_start(rr_glm_sviw *o, const double *z0, const double *lower,
 
 int rr_glm_sviw_run(rr_glm_sviw *o, int64_t steps, const int *d_idx, const float *dE, uint64_t seed, uint64_t key0) {
     RR_REQUIRE(o != nullptr && d_idx != nullptr && steps >= 1 && steps <= (1 << 20), "rr_glm_sviw_run: 1 <= steps <= 2^20 per call");
-    RR_REQUIRE(o->t + steps <= o->maxiter, "rr_glm_sviw_run: %lld steps done, %lld more asked, %lld at most", (long long)o->t,
-               (long long)steps, (long long)o->maxiter);
+    RR_REQUIRE(o->st.t + steps <= o->st.maxiter, "rr_glm_sviw_run: %lld steps done, %lld more asked, %lld at most", (long long)o->st.t,
+               (long long)steps, (long long)o->st.maxiter);
     rr_ctx *c = o->ctx;
     RR_CHECK_HIP(hipSetDevice(c->device));
     SwArgs a = o->a;
     const dim3 gi((unsigned)a.nitems, (unsigned)a.K), gb((unsigned)a.nbx, (unsigned)a.K), th(SW_THREADS);
     for (int64_t t = 0; t < steps; ++t) {
-        const int64_t gt = o->t + t;
+        const int64_t gt = o->st.t + t;
         a.idx = d_idx + (size_t)t * a.M;
         a.E = dE ? dE + (size_t)t * a.K * a.L * a.F : nullptr;
         // the key of rr_glm_draw_kernel for (seed, key0 + t); Adam's bias (sgd.py:322-323): nothing of either on the device
-        uint64_t x = (seed ^ ((key0 + (uint64_t)t) * 0xD1B54A32D192ED03ull)) + 0x9E3779B97F4A7C15ull;
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-        a.stepkey = x ^ (x >> 31);
-        a.b1t = 1.0 - pow(a.up[1], (double)(gt + 1));
-        a.b2t = 1.0 - pow(a.up[2], (double)(gt + 1));
+        a.stepkey = rr_svi_stepkey(seed, key0 + (uint64_t)t);
+        rr_svi_adam_bias(a.up, gt + 1, a.b1t, a.b2t);
         a.xin = o->xbuf[gt & 1];
         a.xout = o->xbuf[(gt + 1) & 1];
-        a.obj = o->objs + gt;
-        a.norm = o->norms + gt;
+        a.obj = o->st.objs + gt;
+        a.norm = o->st.norms + gt;
         a.objective_only = 0;
         if (o->gm) {   // (the launch counters of the bounds build know an instance by the kernel's name alone)
             hipLaunchKernelGGL(rr_glm_sviw_a_kernel<true>, gi, th, o->lds_bytes, c->stream, a);
@@ -1137,7 +994,7 @@ int rr_glm_sviw_run(rr_glm_sviw *o, int64_t steps, const int *d_idx, const float
         }
     }
     RR_CHECK_HIP(hipGetLastError());
-    o->t += steps;
+    o->st.t += steps;
     return RR_OK;
 }
 
@@ -1148,30 +1005,16 @@ int rr_glm_sviw_starts(rr_glm_sviw *o, int ncand, const int *d_idx, const double
     rr_ctx *c = o->ctx;
     RR_CHECK_HIP(hipSetDevice(c->device));
     SwArgs a = o->a;
-    const size_t want = (size_t)ncand * a.np;
-    if (o->cand_cap < want || o->out_cap < (size_t)ncand) {
-        RR_CHECK_HIP(hipStreamSynchronize(c->stream));
-        if (o->cand) (void)hipFree(o->cand);
-        if (o->out) (void)hipFree(o->out);
-        o->cand = o->out = nullptr;
-        o->cand_cap = o->out_cap = 0;
-        RR_CHECK_HIP(hipMalloc((void **)&o->cand, want * 8));
-        RR_CHECK_HIP(hipMalloc((void **)&o->out, (size_t)ncand * 8));
-        o->cand_cap = want;
-        o->out_cap = (size_t)ncand;
-    }
-    RR_CHECK_HIP(hipMemcpyAsync(o->cand, cand_host, want * 8, hipMemcpyHostToDevice, c->stream));
+    const int rc = rr_svi_state_candidates(o->st, c, ncand, cand_host);
+    if (rc != RR_OK) return rc;
     const dim3 gi((unsigned)a.nitems, (unsigned)a.K), gb((unsigned)a.nbx, (unsigned)a.K), th(SW_THREADS);
     for (int s = 0; s < ncand; ++s) {
         a.idx = d_idx + (size_t)s * a.M;
         a.E = dE ? dE + (size_t)s * a.K * a.L * a.F : nullptr;
-        uint64_t x = (seed ^ ((key0 + (uint64_t)s) * 0xD1B54A32D192ED03ull)) + 0x9E3779B97F4A7C15ull;
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-        a.stepkey = x ^ (x >> 31);
-        a.xin = o->cand + (size_t)s * a.np;
+        a.stepkey = rr_svi_stepkey(seed, key0 + (uint64_t)s);
+        a.xin = o->st.cand + (size_t)s * a.np;
         a.xout = nullptr;
-        a.obj = o->out + s;
+        a.obj = o->st.out + s;
         a.norm = nullptr;
         a.objective_only = 1;
         if (o->gm) {
@@ -1185,21 +1028,14 @@ int rr_glm_sviw_starts(rr_glm_sviw *o, int ncand, const int *d_idx, const double
         }
     }
     RR_CHECK_HIP(hipGetLastError());
-    RR_CHECK_HIP(hipMemcpyAsync(objs_host, o->out, (size_t)ncand * 8, hipMemcpyDeviceToHost, c->stream));
+    RR_CHECK_HIP(hipMemcpyAsync(objs_host, o->st.out, (size_t)ncand * 8, hipMemcpyDeviceToHost, c->stream));
     RR_CHECK_HIP(hipStreamSynchronize(c->stream));
     return RR_OK;
 }
 
 int rr_glm_sviw_read(rr_glm_sviw *o, double *z, double *objs, double *norms, int64_t *steps) {
     RR_REQUIRE(o != nullptr, "rr_glm_sviw_read: null argument");
-    rr_ctx *c = o->ctx;
-    RR_CHECK_HIP(hipSetDevice(c->device));
-    RR_CHECK_HIP(hipStreamSynchronize(c->stream));
-    if (z) RR_CHECK_HIP(hipMemcpy(z, o->a.z, (size_t)o->a.np * 8, hipMemcpyDeviceToHost));
-    if (objs && o->t) RR_CHECK_HIP(hipMemcpy(objs, o->objs, (size_t)o->t * 8, hipMemcpyDeviceToHost));
-    if (norms && o->t) RR_CHECK_HIP(hipMemcpy(norms, o->norms, (size_t)o->t * 8, hipMemcpyDeviceToHost));
-    if (steps) *steps = o->t;
-    return RR_OK;
+    return rr_svi_state_read(o->st, o->ctx, z, objs, norms, steps);
 }
 
 void rr_glm_sviw_destroy(rr_glm_sviw *o) {

@@ -11,9 +11,9 @@ tests/test_sampler_cases_host.py and tests/test_gpu_sampler_exact.py).
     e   = sqrt(-2 ln u1) cos(2 pi u2)
 
 The device evaluates the last line in float32 (__logf, the hardware cosine on revolutions); the model in float64 from the
-same two integers.  The kernels that hold a copy of the generator: rr_glm_draw_kernel (rr_elbo.hip: rr_featmat_glm_step_sampled
-and the resident step rr_glm_sgd_step) and svi_draw / svi_draws (rr_svi.hip: the fused loop's step 0, its prefetch of step
-t + 1, and the random starts).  The fused loop's launch step t uses step = key0 + t, candidate c of its starts step = key0 + c.
+same two integers.  The generator is rr_svi_stepkey / rr_svi_draw (rr_svi_common.h); the kernels that call it: rr_glm_draw_kernel
+(rr_elbo.hip: rr_featmat_glm_step_sampled and the resident step rr_glm_sgd_step), svi_draws (rr_svi.hip: the fused loop's step
+0, its prefetch of step t + 1, and the random starts) and sw_draws (rr_svi_wide.hip).  The fused loop's launch step t uses step = key0 + t, candidate c of its starts step = key0 + c.
 
 The identity set-up: a linear child without the column of ones on X = I_F, Gaussian likelihood with variance 1, y = 0, m = 0,
 C a power of four.  The latent value of row r under weight sample kl is then the weight itself, w = sqrt(C) e, exactly -- the

@@ -3,8 +3,8 @@ against float64 over their whole range: tails, the 1 + t == 1 switch of log1p, t
 large binomial n (tests/lik_cases.py: domain, grid, references, bound).
 
 Three device implementations exist: rr_glm_lik_kernel (float32, after the first GEMM; RR_GLM_FUSE_LIK=0), the epilogue of
-rr_gemm_lik_f32_kernel (float32; RR_GLM_FUSE_LIK=force) -- both through rr_lik_elem, rr_elbo.hip -- and svi_lik (float64,
-rr_svi.hip) in the fused small-minibatch loop.
+rr_gemm_lik_f32_kernel (float32; RR_GLM_FUSE_LIK=force) -- both through rr_lik_elem, rr_elbo.hip -- and rr_svi_lik (float64,
+rr_svi_common.h) in the fused small-minibatch loop.
 
 With X an identity matrix and K L a power of two the step's latent values are the weight samples themselves: the upload
 scales by 1 / (K L), the product with a 1 is exact, the kernel scales back by K L.  Edws[kl][r] is then the single element
@@ -177,7 +177,7 @@ SVI_M, SVI_K, SVI_L = 20, 4, 2
 
 @pytest.mark.parametrize("lik", lc.LIKS)
 def test_fused_float64_kernel_over_the_range(lik):
-    """svi_lik (rr_svi.hip:138) through one plain SGD step of the fused small-minibatch loop: one ("linear", M, False, I_M)
+    """rr_svi_lik (rr_svi_common.h:46) through one plain SGD step of the fused small-minibatch loop: one ("linear", M, False, I_M)
     child, M = 20 rows, K = 4 components, one band of the grid restricted to [-200, 40] per component, zero draws and C = 1e-12,
     so that w = m and f[j][k] = m[j][k]; target (j + s) mod nt on row j, one step per s: every (target, latent value) pair
     occurs.  (z0 - z1) / eta with eta = 1 is the gradient the kernel formed and objs[0] its -ELBO; against orc.glm_elbo, per

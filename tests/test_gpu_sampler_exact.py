@@ -5,7 +5,7 @@ weight sample, feature) a draw is -- in every kernel that holds a copy of the ge
   A  rr_featmat_glm_step_sampled (rr_glm_draw_kernel, rr_elbo.hip), both likelihood routes, F on and across a 256-column pad
      block, a seed beyond 2^31, K L factored three ways, after a wider step has grown the scratch;
   B  ResidentSgd.step (the same kernel launched by rr_glm_sgd_step), one and two streams, one step and three;
-  C  FusedSvi.run (svi_draw, rr_svi.hip: step 0 and the prefetch of step t + 1), F even and odd, launches cut 3 and 2 + 1;
+  C  FusedSvi.run (rr_svi_draw, rr_svi_common.h, in rr_svi.hip's svi_draws: step 0 and the prefetch of step t + 1), F even and odd, launches cut 3 and 2 + 1;
   D  FusedSvi.starts (candidate c on step key0 + c);
   E  the keys glm.py hands down over a fit: 0 .. nstarts - 1 to the starts, then consecutive, a new seed per fit.
 
@@ -254,7 +254,7 @@ class _Fused(object):
 def test_fused_single_step_draws_are_the_steps(F):
     """A one-step launch, K = 4, L = 1, on each of the three row sets: z1[f K + k] = -eta bmag e[k][f] / K exactly for the
     features f whose row the step took (the kernel is float64 throughout), exactly 0 for the others, and e is array_equal to
-    A's draws -- svi_draw and rr_glm_draw_kernel are the same float32 expression.  F = 38: the kernel's row length in LDS is 39."""
+    A's draws -- svi_draws and rr_glm_draw_kernel call the same float32 expression, rr_svi_draw.  F = 38: the kernel's row length in LDS is 39."""
     K, seed = sc.LOOP_K, sc.LOOP_SEED
     seen = np.zeros(F, dtype=bool)
     for key in sc.LOOP_KEYS:
